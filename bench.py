@@ -16,6 +16,14 @@ Prints ONE JSON line on rank 0 (contract in the task statement), with
 `roofline` (INT32 VALU bound, algorithmic work of Go's 4-bit-window
 Montgomery ladder) and `cpu_baseline` (the C restatement of Go
 expNNMontgomery timed on this host's cores, rank 0, N=1 only).
+
+A plain run (`--gpus G --steps K --warmup W`) does the headline alone: set-up,
+warm-up, the K timed steps, the result line (its roofline from the timed
+steps' own events, `cpu_baseline` null). `--full` adds everything else: the
+untimed checks of the outputs (pow() sample, whole-batch digest), GPU
+telemetry, the CPU baselines, the per-operand-exponent shapes, configs 1, 3, 4
+and 5, and the detail file. `--dump-outputs DIR` writes the last timed step's
+results to DIR (dump_outputs) in either mode.
 """
 from __future__ import annotations
 
@@ -282,6 +290,34 @@ def synth_bases(N2: int, count: int, seed: int, words: int) -> np.ndarray:
     top = (N2 >> (32 * (words - 1))) & 0xFFFFFFFF
     x[:, words - 1] = x[:, words - 1] % max(top, 1)
     return x
+
+
+DUMP_MAX_BYTES = 32 << 20      # per dumped array: well inside 64 MB for the whole directory
+DUMP_SAMPLE_SEED = 0x64756D70  # the sampled operands are the same in every run and every build
+
+
+def dump_rows(count: int, words: int) -> np.ndarray:
+    """The operands --dump-outputs writes: all of them while count x words
+    float64 fit in DUMP_MAX_BYTES, else a fixed, seeded sample (ascending)."""
+    keep = max(1, DUMP_MAX_BYTES // (8 * words))
+    if count <= keep:
+        return np.arange(count, dtype=np.int64)
+    rows = np.random.default_rng(DUMP_SAMPLE_SEED).choice(count, size=keep, replace=False)
+    return np.sort(rows).astype(np.int64)
+
+
+def dump_outputs(dirname: str, name: str, out: np.ndarray) -> None:
+    """--dump-outputs: what the caller of the timed path holds after the last
+    timed step -- the results x^N mod m as little-endian 32-bit words, one
+    operand per row -- as DIR/<name>.npy, float64 (every 32-bit word is exact),
+    rows dump_rows() of the batch; DIR/<name>_rows.npy holds their operand
+    indices. The inputs are seeded (synth_bases), so two builds run with the
+    same arguments write arrays that compare element for element."""
+    out = np.ascontiguousarray(out).view(np.uint32)
+    rows = dump_rows(out.shape[0], out.shape[1])
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + ".npy"), out[rows].astype(np.float64))
+    np.save(os.path.join(dirname, name + "_rows.npy"), rows.astype(np.float64))
 
 
 def host_info() -> dict:
@@ -1196,6 +1232,8 @@ def node_main(args, progress) -> None:
     el = time.perf_counter() - t0
     kms = [p["ev"][0].elapsed_time(p["ev"][1]) / max(1, args.steps) for p in per]
     launches = [mpcx.device_launches(d) - l0[d] for d in range(D)]
+    if args.dump_outputs:  # device 0's batch (the directory stays within its size bound for any device count)
+        dump_outputs(args.dump_outputs, "modexp_out", per[0]["o"].cpu().numpy())
     bad = []
     for p in per:  # untimed: sampled outputs of every device against pow()
         out = p["o"].cpu().numpy().view(np.uint32)
@@ -1353,6 +1391,12 @@ def main():
     ap.add_argument("--node-devices", type=int, default=0, help="--node: GPUs to bind (0: all visible)")
     ap.add_argument("--node-dup", type=int, default=0,
                     help="--node rehearsal: bind HIP ordinal 0 this many times as logical devices")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline (config 2: set-up, warm-up, timed steps, result line): the untimed "
+                         "checks of its outputs, GPU telemetry, the CPU baselines, configs 1, 3, 4 and 5, the "
+                         "per-operand-exponent shapes and the detail file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
     if args.node:
         if int(os.environ.get("WORLD_SIZE", "1")) != 1:
@@ -1367,6 +1411,11 @@ def main():
         sys.exit(relaunch_under_torchrun(args, sys.argv[1:]))
     if int(os.environ.get("WORLD_SIZE", "1")) != args.gpus:
         sys.exit(f"bench.py: WORLD_SIZE={os.environ.get('WORLD_SIZE')} but --gpus {args.gpus}")
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1 (ms_per_step is the timed region over the steps)")
+    # a plain run is the headline alone: set-up, warm-up, the timed steps, the
+    # outputs if asked for, the result line. Everything else needs --full.
+    full = args.full
     # progress lines on stderr (stdout carries the one JSON line): phases
     # here, keygen waves from the C++ driver
     os.environ.setdefault("MPCX_PROGRESS", "1")
@@ -1381,6 +1430,8 @@ def main():
 
     def progress(msg):
         print(f"[bench {time.time() - t_start:7.1f} s] {msg}", file=sys.stderr, flush=True)
+        if not full:
+            return
         try:
             os.makedirs(os.path.dirname(maps_path), exist_ok=True)
             with open("/proc/self/maps") as fi, open(maps_path, "w") as fo:
@@ -1396,20 +1447,21 @@ def main():
     local = gpu_index()
     # clock / power / temperature of this rank's GPU over the timed region
     # (rank 0; a separate process, started before this one initialises the GPU)
-    smi = SmiSampler(local) if rank == 0 and not args.no_smi else None
+    smi = SmiSampler(local) if full and rank == 0 and not args.no_smi else None
     # The signing CPU baseline forks worker processes: run it before this
     # process touches the GPU.
     info = host_info()
     if args.cpu_threads:
         info["usable_threads"] = args.cpu_threads
     sign_cpu = sign3_cpu = None
-    if args.wallets > 0 and rank == 0 and world == 1 and not args.no_cpu_baseline:
+    cpu_legs = full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    if args.wallets > 0 and cpu_legs:
         progress("CPU baseline: signing")
         sign_cpu = cpu_baseline_signing(args.cpu_sign_seconds, info, args.signers)
         if args.signers != 3:
             sign3_cpu = cpu_baseline_signing(args.cpu_sign_seconds, info, 3)
     keygen_cpu = None
-    if args.keygen_sessions > 0 and rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.keygen_sessions > 0 and cpu_legs:
         progress("CPU baseline: keygen proofs")
         keygen_cpu = cpu_baseline_keygen(16.0, info, args.parties)
     if world > 1:
@@ -1488,9 +1540,12 @@ def main():
     step_ms = [a.elapsed_time(b) for a, b in evs]
     smi_window = smi.window(w0, w1) if smi else None
 
+    if args.dump_outputs and rank == 0:  # rank 0's batch, as the last timed step left it
+        dump_outputs(args.dump_outputs, "modexp_out", d_out.cpu().numpy())
+
     # untimed correctness sample of the last step's outputs (after the timed
     # region so that --warmup 0 still checks real results)
-    if args.verify and args.steps + args.warmup > 0:
+    if full and args.verify and args.steps + args.warmup > 0:
         out = d_out.cpu().numpy().view(np.uint32)
         idx = np.linspace(0, count - 1, args.verify).astype(int)
         xs = mpcx.words_to_ints(bases[idx])
@@ -1503,7 +1558,7 @@ def main():
     # (tests/golden/batch_digest.json, untimed)
     digest = None
     gd_path = os.path.join(ROOT, "tests", "golden", "batch_digest.json")
-    if rank == 0 and args.modbits == 4096 and args.steps + args.warmup > 0 and os.path.exists(gd_path):
+    if full and rank == 0 and args.modbits == 4096 and os.path.exists(gd_path):
         gd = json.load(open(gd_path))
         if gd["count"] == count and gd["words"] == words:
             import hashlib
@@ -1555,7 +1610,7 @@ def main():
                 "checked": "8 sampled operands vs pow()"}
 
     sub_lines = None
-    if rank == 0 and args.extra_lines and args.modbits == 4096:
+    if full and rank == 0 and args.extra_lines and args.modbits == 4096:
         progress("config 2: per-operand exponents")
         sub_lines = [per_operand(2048), per_operand(4096)]
 
@@ -1624,6 +1679,13 @@ def main():
         result["batch_digest"] = digest
     if sub_lines:
         result["config2_per_operand_exponents"] = sub_lines
+    if not full:  # the plain run ends here: no other config, no baseline, no detail file
+        progress("done")
+        if rank == 0:
+            print(json.dumps(compact_line(result, None)), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         progress("CPU baseline: config 2")
         result["cpu_baseline"] = cpu_baseline(N, args.cpu_seconds, info)

@@ -108,6 +108,41 @@ def test_gpus_without_launcher_relaunches_under_torchrun(monkeypatch):
     assert cmd[-4:] == ["--gpus", "4", "--steps", "3"]
 
 
+def test_dump_rows_fixed_sample_within_size_bound():
+    """--dump-outputs: every operand of a small batch, a fixed ascending sample of
+    a batch whose float64 words would pass DUMP_MAX_BYTES (the bench's 65,536 x
+    128 words is exactly twice the bound), the same rows on every call."""
+    import numpy as np
+    assert list(bench.dump_rows(5, 128)) == [0, 1, 2, 3, 4]
+    keep = bench.DUMP_MAX_BYTES // (8 * 128)
+    assert list(bench.dump_rows(keep, 128)) == list(range(keep))
+    rows = bench.dump_rows(65536, 128)
+    assert len(rows) == keep == 32768 and rows.dtype == np.int64
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < 65536
+    assert np.array_equal(rows, bench.dump_rows(65536, 128))
+    assert len(bench.dump_rows(keep + 1, 128)) == keep
+
+
+def test_dump_outputs_writes_exact_float64_words(tmp_path):
+    import numpy as np
+    out = np.array([[0, 1, 0xFFFFFFFF], [0x80000000, 0x12345678, 7]], dtype=np.uint32)
+    d = tmp_path / "dump" / "nested"
+    bench.dump_outputs(str(d), "modexp_out", out.view(np.int32))  # the device tensor's dtype is int32
+    got = np.load(d / "modexp_out.npy")
+    assert got.dtype == np.float64 and got.shape == (2, 3)
+    assert np.array_equal(got.astype(np.uint64), out.astype(np.uint64))
+    assert np.array_equal(np.load(d / "modexp_out_rows.npy"), np.array([0.0, 1.0]))
+    assert sorted(p.name for p in d.iterdir()) == ["modexp_out.npy", "modexp_out_rows.npy"]
+
+
+def test_steps_must_be_positive(monkeypatch):
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "0"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert "--steps" in str(e.value.code)
+
+
 def test_mx_executed_floor_counts_the_schedule():
     """bench.mx_floor: the executed-work floor of k_modexp_mx counts
     the sliding-window schedule of the exponent and prices the product loops' MADs

@@ -203,7 +203,7 @@ def test_bench_two_ranks(gpu, tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     detail = tmp_path / "detail.json"
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
            "--count", "4096", "--wallets", "300", "--keygen-sessions", "64", "--keygen-wave", "32",
            "--safe-primes", "8", "--no-cpu-baseline", "--no-smi", "--detail", str(detail)]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=root)
@@ -220,6 +220,47 @@ def test_bench_two_ranks(gpu, tmp_path):
     full = json.load(open(detail))
     assert full["signing"]["signatures_verified"] == 600
     assert full["keygen"]["sessions"] == 64
+
+
+def test_bench_plain_run_is_the_headline_alone(gpu, tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the config-2
+    headline only (no other config, no CPU baseline, no detail file), K timed
+    steps in ms_per_step, and --dump-outputs writes the last step's results as
+    float64 words that equal pow() on the seeded bases. 4,163 operands: the
+    matrix-core kernel's range, not a whole number of workgroups."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "dump"
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    count = 4163
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+           "--count", str(count), "--dump-outputs", str(dump)]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280, cwd=tmp_path)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [x for x in r.stdout.splitlines() if x.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == 1 and line["steps"] == 3 and line["warmup"] == 1
+    assert line["unit"] == "modexp/s" and line["higher_is_better"] is True and line["dtype"] == "u32"
+    assert line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(count / (line["ms_per_step"] * 1e-3), rel=1e-4)
+    assert line["roofline"]["kernel_ms"] <= line["ms_per_step"]
+    assert line["cpu_baseline"] is None and line["configs"] == {} and line["detail"] is None
+    assert "digest_match" not in line
+    assert sorted(p.name for p in tmp_path.iterdir()) == ["dump"]  # nothing else written beside the outputs
+    got = np.load(dump / "modexp_out.npy")
+    assert got.dtype == np.float64 and got.shape == (count, 128)
+    assert np.array_equal(np.load(dump / "modexp_out_rows.npy"), np.arange(count, dtype=np.float64))
+    N = bench.load_key()
+    bases = bench.synth_bases(N * N, count, 0x6D706332, 128)
+    idx = [0, 1, 2047, 2048, 4159, 4160, count - 1]
+    xs = gpu.words_to_ints(bases[idx])
+    zs = gpu.words_to_ints(got[idx].astype(np.uint32))
+    assert zs == [pow(x, N, N * N) for x in xs]
 
 
 def test_bench_node_mode(gpu, tmp_path):

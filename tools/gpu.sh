@@ -3,7 +3,7 @@
 # first failure (fault, abort, timeout) ends the call.
 #
 #   bash tools/gpu.sh suite  OUT                 pytest -m gpu + smoke
-#   bash tools/gpu.sh bench  OUT [bench args]    bench.py -> OUT/bench.json + summary
+#   bash tools/gpu.sh bench  OUT [bench args]    bench.py --full -> OUT/bench.json + summary
 #   bash tools/gpu.sh trace  OUT [bench args]    rocprofv3 --kernel-trace --stats of bench.py + segments
 #   bash tools/gpu.sh pmc    OUT COUNTERS [bench args]   one rocprofv3 --pmc pass (COUNTERS comma-free, space-joined in quotes)
 #   bash tools/gpu.sh ab     OUT N LIB_A LIB_B [bench args]  N interleaved config-2 runs per libmpcx build
@@ -46,10 +46,10 @@ suite)
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 || { tail $O/smoke.txt; exit 1; }
   tail -2 $O/smoke.txt ;;
 bench)
-  timeout -k 10 900 python3 bench.py --detail $O/bench_detail.json "$@" > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
+  timeout -k 10 900 python3 bench.py --full --detail $O/bench_detail.json "$@" > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
   wc -c $O/bench.json; summ $O/bench_detail.json ;;
 trace)
-  timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python3 bench.py \
+  timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o bench -- python3 bench.py --full \
       --detail $O/bench_detail.json "$@" > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; }
   summ $O/bench_detail.json
   f=$(find $O/prof -name '*kernel_trace.csv' | head -1)
@@ -57,14 +57,14 @@ trace)
   find $O/prof -name '*kernel_stats*' -exec cp {} $O/kernel_stats.csv \; ;;
 pmc)
   ctr=$1; shift
-  timeout -s KILL 300 rocprofv3 --pmc $ctr --output-format csv -d $O/prof -o pmc -- python3 bench.py --detail $O/bench_detail.json "$@" \
+  timeout -s KILL 300 rocprofv3 --pmc $ctr --output-format csv -d $O/prof -o pmc -- python3 bench.py --full --detail $O/bench_detail.json "$@" \
       > $O/bench.json 2> $O/bench.err || { tail $O/bench.err; exit 1; } ;;
 ab)
   n=$1; la=$2; lb=$3; shift 3
   for i in $(seq 1 $n); do
     for lib in $la $lb; do
       [ $lib = $la ] && tag=A_$i || tag=B_$i
-      MPCX_LIB_PATH=$(realpath $lib) timeout -k 10 300 python3 bench.py --detail $O/ab_$tag.json "$@" > $O/ab_$tag.line \
+      MPCX_LIB_PATH=$(realpath $lib) timeout -k 10 300 python3 bench.py --full --detail $O/ab_$tag.json "$@" > $O/ab_$tag.line \
           2> $O/ab_$tag.err || { tail $O/ab_$tag.err; exit 1; }
       echo -n "$lib run $i: "; summ $O/ab_$tag.json short
     done
@@ -78,7 +78,7 @@ abswap)
     for lib in $la $lb; do
       [ $lib = $la ] && tag=A_$i || tag=B_$i
       cp $lib mpcium_amd/libmpcx.so.tmp && mv mpcium_amd/libmpcx.so.tmp mpcium_amd/libmpcx.so
-      timeout -k 10 600 python3 bench.py --detail $O/ab_$tag.json "$@" > $O/ab_$tag.line 2> $O/ab_$tag.err
+      timeout -k 10 600 python3 bench.py --full --detail $O/ab_$tag.json "$@" > $O/ab_$tag.line 2> $O/ab_$tag.err
       rc=$?
       cp $O/orig_libmpcx.so mpcium_amd/libmpcx.so
       [ $rc -eq 0 ] || { tail $O/ab_$tag.err; exit 1; }
@@ -95,7 +95,7 @@ abn)
     for lib in ${libs//,/ }; do
       k=$((k+1)); tag=L${k}_$i
       cp $lib mpcium_amd/libmpcx.so.tmp && mv mpcium_amd/libmpcx.so.tmp mpcium_amd/libmpcx.so
-      timeout -k 10 600 python3 bench.py --detail $O/ab_$tag.json "$@" > $O/ab_$tag.line 2> $O/ab_$tag.err
+      timeout -k 10 600 python3 bench.py --full --detail $O/ab_$tag.json "$@" > $O/ab_$tag.line 2> $O/ab_$tag.err
       rc=$?
       cp $O/orig_libmpcx.so mpcium_amd/libmpcx.so
       [ $rc -eq 0 ] || { tail $O/ab_$tag.err; exit 1; }
@@ -113,7 +113,7 @@ abhost)
     for lib in ${libs//,/ }; do
       k=$((k+1)); tag=H${k}_$i
       cp $lib mpcium_amd/libmpcx_host.so.tmp && mv mpcium_amd/libmpcx_host.so.tmp mpcium_amd/libmpcx_host.so
-      timeout -k 10 600 python3 bench.py --detail $O/ab_$tag.json "$@" > $O/ab_$tag.line 2> $O/ab_$tag.err
+      timeout -k 10 600 python3 bench.py --full --detail $O/ab_$tag.json "$@" > $O/ab_$tag.line 2> $O/ab_$tag.err
       rc=$?
       cp $O/orig_libmpcx_host.so mpcium_amd/libmpcx_host.so
       [ $rc -eq 0 ] || { tail $O/ab_$tag.err; exit 1; }
@@ -126,7 +126,7 @@ envab)
   for i in $(seq 1 $n); do
     for e in A B; do
       [ $e = A ] && ev="$ea" || ev="$eb"
-      env $ev timeout -k 10 600 python3 bench.py --detail $O/ab_${e}_$i.json "$@" > $O/ab_${e}_$i.line 2> $O/ab_${e}_$i.err \
+      env $ev timeout -k 10 600 python3 bench.py --full --detail $O/ab_${e}_$i.json "$@" > $O/ab_${e}_$i.line 2> $O/ab_${e}_$i.err \
           || { tail $O/ab_${e}_$i.err; exit 1; }
       echo "== $e ($ev) run $i"; summ $O/ab_${e}_$i.json
     done
@@ -139,7 +139,7 @@ envn)
     k=0
     for ev in "${EV[@]}"; do
       k=$((k+1)); tag=E${k}_$i
-      env $ev timeout -k 10 600 python3 bench.py --detail $O/ab_$tag.json "$@" > $O/ab_$tag.line 2> $O/ab_$tag.err \
+      env $ev timeout -k 10 600 python3 bench.py --full --detail $O/ab_$tag.json "$@" > $O/ab_$tag.line 2> $O/ab_$tag.err \
           || { tail $O/ab_$tag.err; exit 1; }
       echo "== $tag ($ev)"; summ $O/ab_$tag.json short
       python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print('  ', {k: round(d[k]['value'],1) for k in ('signing','signing_3_signers','keygen','paillier_batch') if k in d})" $O/ab_$tag.json
@@ -151,7 +151,7 @@ argab)
   for i in $(seq 1 $n); do
     for e in A B; do
       [ $e = A ] && ex="$aa" || ex="$ab"
-      timeout -k 10 600 python3 bench.py --detail $O/ab_${e}_$i.json $ex "$@" > $O/ab_${e}_$i.line 2> $O/ab_${e}_$i.err \
+      timeout -k 10 600 python3 bench.py --full --detail $O/ab_${e}_$i.json $ex "$@" > $O/ab_${e}_$i.line 2> $O/ab_${e}_$i.err \
           || { tail $O/ab_${e}_$i.err; exit 1; }
       echo "== $e ($ex) run $i"; summ $O/ab_${e}_$i.json
     done

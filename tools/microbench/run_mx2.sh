@@ -5,5 +5,5 @@ O=gpurun_out/mx2; mkdir -p $O
 cat $O/dbg.json $O/chain.json
 timeout -k 10 300 python -u -m pytest tests/test_gpu_mx.py -x -q --timeout 280 --timeout-method thread > $O/tests.txt 2>&1 || { tail -30 $O/tests.txt; exit 1; }
 tail -2 $O/tests.txt
-for mx in 1 0; do timeout -k 10 300 python -u bench.py --steps 5 --warmup 2 --extra-lines 0 --wallets 0 --keygen-sessions 0 --no-cpu-baseline --opt mx=$mx --detail $O/detail_mx$mx.json > $O/bench_mx$mx.json 2> $O/bench_mx$mx.err || { tail $O/bench_mx$mx.err; exit 1; }; python3 -c "
+for mx in 1 0; do timeout -k 10 300 python -u bench.py --full --steps 5 --warmup 2 --extra-lines 0 --wallets 0 --keygen-sessions 0 --no-cpu-baseline --opt mx=$mx --detail $O/detail_mx$mx.json > $O/bench_mx$mx.json 2> $O/bench_mx$mx.err || { tail $O/bench_mx$mx.err; exit 1; }; python3 -c "
 import json; d=json.loads(open('$O/bench_mx$mx.json').read().strip().splitlines()[-1]); print('mx=$mx', d['value'], d['ms_per_step'], d['roofline']['frac'])"; done
