@@ -130,7 +130,7 @@ bool g_dup_device = false;               // mpcx_set_option("duplicate_device", 
 int g_mx = MPCX_MX_DEFAULT;              // mpcx_set_option("mx", 1): geometry-2 batches reduce on the matrix cores
 uint32_t g_mx_min = 2048;                // mpcx_set_option("mx_min", n): smallest batch for k_modexp_mx
 uint32_t g_mx_seg_min = 64;              // mpcx_set_option("mx_seg_min", n): smallest segment of a k_modexp_multi_mx launch (round 6: 64 vs 256, profiles/r06/segmin*)
-double g_mx_step = 0.81;                 // mpcx_set_option("mx_step", 100x): k_modexp_mx's wave-round time / k_modexp's (0: model ignores mx)
+double g_mx_step = 0.81;                 // mpcx_set_option("mx_step", 100x): k_modexp_mx's wave-round time / k_modexp's (100: model ignores mx)
 double g_geom_tput = 0.0;                // mpcx_set_option("geom_tput", 100x): GPU-share weight of the launch-time model
 struct Staging {
   void* ptr = nullptr;
@@ -1205,6 +1205,258 @@ int main_geom_for(const mpcx_modulus_s* mod, bool ops_fit) {
   return geom_serves(g, mod, ops_fit) ? g : MPCX_FULL_GEOM(mod->cls);
 }
 
+// ---- launch plan of the modexp batch entry points (single and multi batch)
+
+// Does a launch in geometry g of `total` operands run on the matrix cores?
+// A single batch runs k_modexp_mx: the 4096-bit main geometry (mx >= 1), the
+// 2048-bit lane pair only on request (mx = 2: it measured slower,
+// profiles/r05/mx/g5/). A multi-batch launch runs k_modexp_multi_mx: geometry 2
+// only, when the launch is large and its smallest non-empty segment min_seg
+// fills at least one workgroup's worth of its tables (the single batch has no
+// segment rule).
+bool runs_on_mx(int g, uint32_t total, uint32_t min_seg, bool multi) {
+  const bool has_kernel = g == 2 || (g == 5 && !multi && g_mx >= 2);
+  return g_mx && has_kernel && total >= g_mx_min && (!multi || min_seg >= g_mx_seg_min);
+}
+
+// Launch-time model of the 4096-bit class's geometries, measured on MI355X
+// (tools/geom_sweep.py, profiles/r02/geom_sweep/): a launch of W wavefronts
+// takes about c0 + s * k with k = ceil(W / SIMDs) wavefronts per SIMD, in units
+// of the main geometry's time per wavefront-per-SIMD step. Per operand the main
+// geometry does the least work, but its 16 operands per wavefront leave most
+// SIMDs idle or one wave short on batches of a fraction of a round; the mid
+// geometry (8 operands per wavefront, 3 resident per SIMD) and the narrow one (2
+// per wavefront) trade per-operand work for a finer split. x^N mod N^2 for
+// 1.25K / 5K / 10K / 20K / 30K / 40K operands: main 49 / 49 / 50 / 91 / 93 / 135 ms,
+// mid 32 / 32 / 55 / 83 / 107 / 134 ms, narrow 20 / 41 / 65 / 119 / 175 / 230 ms.
+//
+// The 2048-bit class keeps the narrow_rounds threshold: the same kind of model
+// fitted to its geometries (tools/geom_sweep.py --class 1,
+// profiles/r04/geom_sweep_c1/: lane pair 25.4 ms per wavefront-per-SIMD step,
+// 4 x 19 at 0.556 and 16 x 5 at 0.226 of it) sent mid-size batches to 4 x 19 and
+// measured 7% slower on config 5's concurrent load (profiles/r04/c1model_ab/).
+// mx_ok: the main geometry's launch would run on the matrix cores (runs_on_mx),
+// whose wave-per-SIMD step is g_mx_step of the CIOS one
+// (config 2: 139.5 vs 172.5 ms, profiles/r06/libab1/ vs profiles/r05/s2/).
+// g_geom_tput > 0 adds that weight x the launch's share of the GPU's SIMD time
+// (s x waves / nsimd) to its latency: under concurrent launches (signing,
+// keygen) the SIMDs a geometry occupies are time the other lanes' kernels lose.
+int fastest_geom(int cls, uint32_t count, int nsimd, bool mx_ok) {
+  struct M {
+    int g;
+    double c0, s;
+  };
+  const M ms[3] = {{MPCX_MAIN_GEOM(cls), 0.10, mx_ok ? g_mx_step : 1.0}, {MPCX_MID_GEOM(cls), 0.12, 0.585},
+                   {MPCX_NARROW_GEOM(cls), 0.20, 0.245}};
+  int best = ms[0].g;
+  double tb = 1e300;
+  for (const M& m : ms) {
+    const uint32_t G = (uint32_t)MPCX_GEOM_G(m.g);
+    const double waves = (double)((count + G - 1) / G);
+    const double t = m.c0 + m.s * std::ceil(waves / (double)std::max(1, nsimd)) +
+                     g_geom_tput * m.s * waves / (double)std::max(1, nsimd);
+    if (t < tb) {
+      tb = t;
+      best = m.g;
+    }
+  }
+  return best;
+}
+
+// The one geometry of a launch of `count` operands of class cls (a multi-batch
+// launch takes one for all its segments): the forced geometry, or policy 2's
+// main, or policy 1's launch-time model, or the thresholds. main_serves /
+// forced_serves: the class's main / the forced geometry serves every modulus
+// and operand of the launch (geom_serves); otherwise the full-width one runs.
+int choose_geom(const Device& dev, int cls, uint32_t count, bool main_serves, bool forced_serves, bool mx_ok) {
+  const int gm = main_serves ? g_main_geom[cls] : MPCX_FULL_GEOM(cls);
+  const int gn = MPCX_NARROW_GEOM(cls), gmid = MPCX_MID_GEOM(cls);
+  if (g_force_geom >= 0 && MPCX_GEOM_CLASS(g_force_geom) == cls)
+    return forced_serves ? g_force_geom : MPCX_FULL_GEOM(cls);
+  // policy 2, throughput: the main geometry at every size (concurrent launches
+  // from other lanes fill the SIMDs a small batch leaves idle)
+  if (g_geom_policy == 2) return gm;
+  if (g_geom_policy == 1 && gmid >= 0 && gn >= 0) return fastest_geom(cls, count, dev.num_cus * 4, mx_ok && main_serves);
+  // Measured on MI355X (profiles/r01): a lone wavefront issues v_mad_u64_u32
+  // at ~45% of SIMD peak, so tiny batches (< 0.15 of a round) finish sooner
+  // spread over the narrow geometry's 3x more wavefronts; from ~0.3 rounds up
+  // the main geometry wins, and a narrow tail launch did not pay (round 1).
+  const uint32_t G = (uint32_t)MPCX_GEOM_G(gm);
+  const double rounds = (double)((count + G - 1) / G) / (double)std::max(1, dev.geom_slots[gm]);
+  if (gn >= 0 && rounds < g_narrow_rounds) return gn;
+  return gm;
+}
+
+// Width and null checks of one batch's buffers (count > 0: an empty batch's
+// may be null). `pre` is "" for the single-batch entry points and "group i: "
+// for a multi-batch group; each keeps its own wording (cgo callers log it): the
+// single batch's carries the limits, a group's names the field.
+int check_batch(const char* pre, const mpcx_modulus_s* mod, uint32_t count, const uint32_t* bases,
+                uint32_t base_words, const uint32_t* exps, uint32_t exp_words, const uint32_t* muls,
+                uint32_t mul_words, const uint32_t* out, uint32_t out_words) {
+  const bool grp = *pre;
+  const uint32_t cw = (uint32_t)MPCX_CLASS_WORDS(mod->cls);
+  if (base_words == 0 || base_words > cw)
+    return grp ? fail(MPCX_EINVAL, "%sbase_words %u", pre, base_words)
+               : fail(MPCX_EINVAL, "base_words %u outside [1, %u] (reduce mod m first)", base_words, cw);
+  if (muls && (mul_words == 0 || mul_words > cw))
+    return grp ? fail(MPCX_EINVAL, "%smul_words", pre)
+               : fail(MPCX_EINVAL, "mul_words %u outside [1, %u]", mul_words, cw);
+  if (out_words < mod->words)
+    return grp ? fail(MPCX_EINVAL, "%sout_words < modulus words", pre)
+               : fail(MPCX_EINVAL, "out_words %u < modulus words %u", out_words, mod->words);
+  if (count && (!bases || !out || (exp_words && !exps))) return fail(MPCX_EINVAL, "%snull buffer", pre);
+  return MPCX_OK;
+}
+
+// Go-equivalent MACs of a batch with per-operand exponents: each operand's own
+// exponent length (launch log, kernel stats)
+double go_macs_sum(uint32_t mod_bits, const uint32_t* exps, uint32_t exp_words, uint32_t count) {
+  double alg = 0.0;
+  for (uint32_t i = 0; i < count; ++i)
+    alg += go_macs(mod_bits, bit_length_words(exps + (size_t)i * exp_words, exp_words));
+  return alg;
+}
+
+// a shared exponent's sliding-window schedule, built on the launch stream
+int launch_expsched(const uint32_t* d_exp, uint32_t exp_words, uint32_t* sched, hipStream_t st) {
+  mpcx::ExpSchedArgs sa{};
+  sa.exp = d_exp;
+  sa.exp_words = exp_words;
+  sa.max_width = (uint32_t)g_sched_width;
+  sa.sched = sched;
+  hipError_t e = mpcx_launch_expsched(&sa, st);
+  return e == hipSuccess ? MPCX_OK : hip_fail(e, "launch k_expsched");
+}
+
+// Kernel arguments of one batch (a k_modexp launch, or one segment of a
+// k_modexp_multi launch) in geometry geom. dconst: the modulus's constants on
+// the launch's device (mod_const); sched: the shared exponent's schedule or
+// nullptr (fixed window); mx_img: the modulus's Toeplitz tables when the launch
+// runs on the matrix cores (mx_const), else nullptr; nwaves: the batch's
+// wavefronts (read by the mx kernels only).
+mpcx::ModexpArgs modexp_args(const mpcx_modulus_s* mod, int geom, const uint32_t* dconst, uint32_t count,
+                             const uint32_t* base, uint32_t base_words, const uint32_t* exps, uint32_t exp_words,
+                             const uint32_t* mul, uint32_t mul_words, uint32_t* out, uint32_t out_words,
+                             uint32_t* table, uint32_t exp_bits, int exp_shared, const uint32_t* sched,
+                             const uint8_t* mx_img, uint32_t nwaves) {
+  const uint32_t L = (uint32_t)MPCX_GEOM_L(geom);
+  mpcx::ModexpArgs a{};
+  a.nd = dconst + mod->const_off[geom];
+  a.r1d = a.nd + L;
+  a.r2d = a.nd + 2 * L;
+  a.base = base;
+  a.exps = exps;
+  a.mul = mul;
+  a.out = out;
+  a.table = table;
+  a.count = count;
+  a.base_words = base_words;
+  a.exp_words = exp_words;
+  a.mul_words = mul ? mul_words : 0;
+  a.exp_bits = exp_words ? exp_bits : 0;
+  // fixed window: 5 bits for per-operand exponents above 1024 bits (E/5 + 31
+  // table products < E/4 + 15 from 320 bits on; measured +2.4-2.6% on 2048- and
+  // 4096-bit exponents, profiles/r02/win_ab/), Go's 4 bits otherwise
+  a.win_bits = (!exp_shared && a.exp_bits > 1024u && g_fixed_win >= 5) ? 5u : 4u;
+  a.out_words = out_words;
+  a.n0inv = mod->n0inv;
+  a.exp_shared = exp_shared ? 1 : 0;
+  a.sched = sched;
+  a.mx_img = mx_img;
+  a.nwaves = nwaves;
+  return a;
+}
+
+// ---- the comb pair: mpcx_fixedbase_exp_batch is one group of mpcx_fixedbase_multi_batch's
+
+// One comb group's checks, and the windows its launch processes per base (the
+// longest exponent's). `pre` as check_batch's: "" for mpcx_fixedbase_exp_batch,
+// "group i: " for a multi-batch group, each with its own wording.
+int fb_group_check(const mpcx_fixedbase_group_t& g, const char* pre, uint32_t* nwin) {
+  const bool grp = *pre;
+  if (g.nbases == 0 || g.nbases > MPCX_FB_MAX_BASES)
+    return fail(MPCX_EINVAL, "%snbases %u outside [1, %d]", pre, g.nbases, MPCX_FB_MAX_BASES);
+  for (uint32_t t = 0; t < g.nbases; ++t) {
+    if (!g.fbs[t]) return fail(MPCX_EINVAL, "%snull fixed base %u", pre, t);
+    if (g.fbs[t]->mod != g.fbs[0]->mod) return fail(MPCX_EINVAL, "%sfixed bases of different moduli", pre);
+  }
+  mpcx_mod_t mod = g.fbs[0]->mod;
+  const uint32_t cw = (uint32_t)MPCX_CLASS_WORDS(mod->cls);
+  if (g.out_words < mod->words)
+    return grp ? fail(MPCX_EINVAL, "%sout_words < modulus words", pre)
+               : fail(MPCX_EINVAL, "out_words %u < modulus words %u", g.out_words, mod->words);
+  if (g.muls && (g.mul_words == 0 || g.mul_words > cw))
+    return grp ? fail(MPCX_EINVAL, "%smul_words", pre)
+               : fail(MPCX_EINVAL, "mul_words %u outside [1, %u]", g.mul_words, cw);
+  if (g.count == 0) return MPCX_OK;  // an empty group's buffers may be null
+  if (!g.out) return fail(MPCX_EINVAL, "%snull output", pre);
+  for (uint32_t t = 0; t < g.nbases; ++t) {
+    if (g.exp_words[t] && !g.exps[t]) return fail(MPCX_EINVAL, "%snull exponents %u", pre, t);
+    uint32_t bits = 0;
+    for (uint32_t i = 0; i < g.count && g.exp_words[t]; ++i)
+      bits = std::max(bits, bit_length_words(g.exps[t] + (size_t)i * g.exp_words[t], g.exp_words[t]));
+    const uint32_t wb = g.fbs[t]->wbits;
+    if (bits > g.fbs[t]->nwin * wb)
+      return fail(MPCX_EINVAL, "%sexponent of %u bits > fixed-base table's %u", pre, bits, g.fbs[t]->nwin * wb);
+    nwin[t] = (bits + wb - 1) / wb;
+  }
+  return MPCX_OK;
+}
+
+// A comb group's work. alg, Go-equivalent (launch log): one Exp per base per
+// operand. exec, executed (kernel stats): one product per window of each
+// exponent, plus the multiplier's, 2 L^2 MACs each. eb_max: the longest exponent.
+struct FbWork {
+  double alg = 0.0, exec = 0.0;
+  uint32_t eb_max = 0;
+};
+FbWork fb_group_work(const mpcx_fixedbase_group_t& g) {
+  FbWork w;
+  const uint32_t bits = g.fbs[0]->mod->bits;
+  const double l2 = 2.0 * (double)((bits + 31) / 32) * (double)((bits + 31) / 32);
+  for (uint32_t t = 0; t < g.nbases; ++t)
+    for (uint32_t i = 0; i < g.count && g.exp_words[t]; ++i) {
+      const uint32_t b = bit_length_words(g.exps[t] + (size_t)i * g.exp_words[t], g.exp_words[t]);
+      w.alg += go_macs(bits, b);
+      w.exec += (double)((b + g.fbs[t]->wbits - 1) / g.fbs[t]->wbits) * l2;
+      w.eb_max = std::max(w.eb_max, b);
+    }
+  if (g.muls) w.exec += (double)g.count * l2;
+  return w;
+}
+
+// Kernel arguments of one comb group (a k_fixedbase launch, or one segment of a
+// k_fixedbase_multi launch) on device di: its exponents, multipliers and
+// outputs at d_exps / d_mul / d_out.
+int fixedbase_args(const mpcx_fixedbase_group_t& g, int geom, int di, const uint32_t* nwin,
+                   const uint32_t* const* d_exps, const uint32_t* d_mul, uint32_t* d_out, mpcx::FixedBaseArgs* out) {
+  mpcx_mod_t mod = g.fbs[0]->mod;
+  const uint32_t* dconst = nullptr;
+  int rc;
+  if ((rc = mod_const(mod, di, &dconst))) return rc;
+  mpcx::FixedBaseArgs a{};
+  a.nd = dconst + mod->const_off[geom];
+  a.r1d = a.nd + MPCX_GEOM_L(geom);
+  a.r2d = a.nd + 2 * MPCX_GEOM_L(geom);
+  for (uint32_t t = 0; t < g.nbases; ++t) {
+    if ((rc = fb_table(g.fbs[t], di, &a.tables[t]))) return rc;
+    a.exps[t] = d_exps[t];
+    a.exp_words[t] = g.exp_words[t];
+    a.nwin[t] = nwin[t];
+    a.wbits[t] = g.fbs[t]->wbits;
+  }
+  a.nbases = g.nbases;
+  a.mul = g.muls ? d_mul : nullptr;
+  a.mul_words = g.muls ? g.mul_words : 0;
+  a.out = d_out;
+  a.out_words = g.out_words;
+  a.count = g.count;
+  a.n0inv = mod->n0inv;
+  *out = a;
+  return MPCX_OK;
+}
+
 // The layout (geometry) of a modulus's comb tables: its class's full-width
 // geometry. (A lane-pair layout for 2048-bit moduli was 10% faster at 131k
 // operands but 24-30% slower at 16k and neutral end to end, where the comb
@@ -1599,189 +1851,56 @@ int mpcx_modulus_geometry(mpcx_mod_t mod, uint32_t* L, uint32_t* P, uint32_t* K,
 
 // Enqueue one batch on lane `lane` of device `di` (lane locked by the caller;
 // its stream is lane.st).
-//
-// Launch-time model of the 4096-bit class's geometries, measured on MI355X
-// (tools/geom_sweep.py, profiles/r02/geom_sweep/): a launch of W wavefronts
-// takes about c0 + s * k with k = ceil(W / SIMDs) wavefronts per SIMD, in units
-// of the main geometry's time per wavefront-per-SIMD step. Per operand the main
-// geometry does the least work, but its 16 operands per wavefront leave most
-// SIMDs idle or one wave short on batches of a fraction of a round; the mid
-// geometry (8 operands per wavefront, 3 resident per SIMD) and the narrow one (2
-// per wavefront) trade per-operand work for a finer split. x^N mod N^2 for
-// 1.25K / 5K / 10K / 20K / 30K / 40K operands: main 49 / 49 / 50 / 91 / 93 / 135 ms,
-// mid 32 / 32 / 55 / 83 / 107 / 134 ms, narrow 20 / 41 / 65 / 119 / 175 / 230 ms.
-//
-// The 2048-bit class keeps the narrow_rounds threshold: the same kind of model
-// fitted to its geometries (tools/geom_sweep.py --class 1,
-// profiles/r04/geom_sweep_c1/: lane pair 25.4 ms per wavefront-per-SIMD step,
-// 4 x 19 at 0.556 and 16 x 5 at 0.226 of it) sent mid-size batches to 4 x 19 and
-// measured 7% slower on config 5's concurrent load (profiles/r04/c1model_ab/).
-// mx_ok: the main geometry's launch would run on the matrix cores (k_modexp_mx /
-// k_modexp_multi_mx), whose wave-per-SIMD step is g_mx_step of the CIOS one
-// (config 2: 139.5 vs 172.5 ms, profiles/r06/libab1/ vs profiles/r05/s2/).
-// g_geom_tput > 0 adds that weight x the launch's share of the GPU's SIMD time
-// (s x waves / nsimd) to its latency: under concurrent launches (signing,
-// keygen) the SIMDs a geometry occupies are time the other lanes' kernels lose.
-static int fastest_geom(int cls, uint32_t count, int nsimd, bool mx_ok = false) {
-  struct M {
-    int g;
-    double c0, s;
-  };
-  const M ms[3] = {{MPCX_MAIN_GEOM(cls), 0.10, mx_ok ? g_mx_step : 1.0}, {MPCX_MID_GEOM(cls), 0.12, 0.585},
-                   {MPCX_NARROW_GEOM(cls), 0.20, 0.245}};
-  int best = ms[0].g;
-  double tb = 1e300;
-  for (const M& m : ms) {
-    const uint32_t G = (uint32_t)MPCX_GEOM_G(m.g);
-    const double waves = (double)((count + G - 1) / G);
-    const double t = m.c0 + m.s * std::ceil(waves / (double)std::max(1, nsimd)) +
-                     g_geom_tput * m.s * waves / (double)std::max(1, nsimd);
-    if (t < tb) {
-      tb = t;
-      best = m.g;
-    }
-  }
-  return best;
-}
-
-// Single-geometry choice for a launch of `count` operands of class cls (the
-// forced geometry, or policy 2's main, or policy 1's launch-time model, or
-// the thresholds) -- the multi-batch launch takes one geometry for all its
-// segments.
-static int choose_geom(const Device& dev, int cls, uint32_t count, bool main_serves, bool forced_serves,
-                       bool mx_ok = false) {
-  const int gm = main_serves ? g_main_geom[cls] : MPCX_FULL_GEOM(cls);
-  const int gn = MPCX_NARROW_GEOM(cls), gmid = MPCX_MID_GEOM(cls);
-  if (g_force_geom >= 0 && MPCX_GEOM_CLASS(g_force_geom) == cls)
-    return forced_serves ? g_force_geom : MPCX_FULL_GEOM(cls);
-  if (g_geom_policy == 2) return gm;
-  if (g_geom_policy == 1 && gmid >= 0 && gn >= 0) return fastest_geom(cls, count, dev.num_cus * 4, mx_ok && main_serves);
-  const uint32_t G = (uint32_t)MPCX_GEOM_G(gm);
-  const double rounds = (double)((count + G - 1) / G) / (double)std::max(1, dev.geom_slots[gm]);
-  if (gn >= 0 && rounds < g_narrow_rounds) return gn;
-  return gm;
-}
-
 // ops_fit: every base and multiplier is below 2^MPCX_GEOM_RBITS of the class's
-// main geometry (host_ops_below; see geom_serves).
+// main geometry (host_ops_below; see geom_serves). alg_macs: the batch's
+// Go-equivalent MACs where the host has the operands' own exponents (< 0: from
+// exp_bits).
 static int modexp_enqueue(int di, Lane& lane, mpcx_mod_t mod, uint32_t count, const uint32_t* d_bases,
                           uint32_t base_words, const uint32_t* d_exps, uint32_t exp_words, int exp_shared,
                           uint32_t exp_bits, const uint32_t* d_muls, uint32_t mul_words, uint32_t* d_out,
                           uint32_t out_words, bool ops_fit, double alg_macs = -1.0) {
-  const Device& dev = g_devs[di];
-  hipStream_t st = lane.st;
-  const uint32_t class_words = (uint32_t)MPCX_CLASS_WORDS(mod->cls);
-  if (base_words == 0 || base_words > class_words)
-    return fail(MPCX_EINVAL, "base_words %u outside [1, %u] (reduce mod m first)", base_words, class_words);
-  if (d_muls && (mul_words == 0 || mul_words > class_words))
-    return fail(MPCX_EINVAL, "mul_words %u outside [1, %u]", mul_words, class_words);
-  if (out_words < mod->words) return fail(MPCX_EINVAL, "out_words %u < modulus words %u", out_words, mod->words);
+  Device& dev = g_devs[di];
+  int rc;
+  if ((rc = check_batch("", mod, count, d_bases, base_words, d_exps, exp_words, d_muls, mul_words, d_out, out_words)))
+    return rc;
   if (exp_bits > 32u * exp_words) return fail(MPCX_EINVAL, "exp_bits %u > 32*exp_words", exp_bits);
   if (count == 0) return MPCX_OK;
-  if (!d_bases || !d_out || (exp_words && !d_exps)) return fail(MPCX_EINVAL, "null buffer");
   const uint32_t* dconst = nullptr;
-  if (int rc = mod_const(mod, di, &dconst)) return rc;
-  // Geometry plan: whole rounds of resident wavefronts in the main geometry,
-  // the partial last round (or a small batch) in the narrow geometry.
-  struct Part {
-    int geom;
-    uint32_t first, count;
-  } parts[2];
-  int nparts = 0;
-  const int gm = main_geom_for(mod, ops_fit), gn = MPCX_NARROW_GEOM(mod->cls);
-  if (g_force_geom >= 0 && MPCX_GEOM_CLASS(g_force_geom) == mod->cls) {
-    parts[nparts++] = {geom_serves(g_force_geom, mod, ops_fit) ? g_force_geom : MPCX_FULL_GEOM(mod->cls), 0, count};
-  } else {
-    const uint32_t G = (uint32_t)MPCX_GEOM_G(gm);
-    const double waves = (double)((count + G - 1) / G);
-    const double rounds = waves / (double)std::max(1, dev.geom_slots[gm]);
-    // Measured on MI355X (profiles/r01): a lone wavefront issues v_mad_u64_u32
-    // at ~45% of SIMD peak, so tiny batches (< 0.15 of a round) finish sooner
-    // spread over the narrow geometry's 3x more wavefronts; from ~0.3 rounds up
-    // the main geometry wins, and a narrow tail launch did not pay (round 1).
-    const int gmid = MPCX_MID_GEOM(mod->cls);
-    if (g_geom_policy == 2) {
-      // throughput: the main geometry at every size (concurrent launches from
-      // other lanes fill the SIMDs a small batch leaves idle)
-      parts[nparts++] = {gm, 0, count};
-    } else if (g_geom_policy == 1 && gmid >= 0 && gn >= 0) {
-      const bool mx_ok = g_mx && gm == 2 && count >= g_mx_min;  // the main geometry would be k_modexp_mx
-      parts[nparts++] = {fastest_geom(mod->cls, count, dev.num_cus * 4, mx_ok), 0, count};
-    } else if (gn >= 0 && rounds < g_narrow_rounds) {
-      parts[nparts++] = {gn, 0, count};
-    } else {
-      parts[nparts++] = {gm, 0, count};
-    }
-  }
-  size_t ws_words = 0;
-  for (int i = 0; i < nparts; ++i) {
-    const uint32_t G = (uint32_t)MPCX_GEOM_G(parts[i].geom), K = (uint32_t)MPCX_GEOM_K(parts[i].geom);
-    ws_words += (size_t)((parts[i].count + G - 1) / G) * MPCX_TABLE_ENTRIES * K * 64u;
-  }
+  if ((rc = mod_const(mod, di, &dconst))) return rc;
+  const int cls = mod->cls;
+  // a forced geometry is tested with the caller's ops_fit, which was computed
+  // against the main geometry's R (mpcx_modexp_multi_batch rescans the operands
+  // against the forced geometry's)
+  const bool forced_serves =
+      g_force_geom >= 0 && MPCX_GEOM_CLASS(g_force_geom) == cls && geom_serves(g_force_geom, mod, ops_fit);
+  // the model's mx input asks about the main geometry this batch would get, the
+  // full-width one where the configured main cannot serve it (the multi path
+  // asks about the class's default main geometry)
+  const bool mx_ok = runs_on_mx(main_geom_for(mod, ops_fit), count, count, false);
+  const int geom = choose_geom(dev, cls, count, geom_serves(g_main_geom[cls], mod, ops_fit), forced_serves, mx_ok);
+  const uint32_t G = (uint32_t)MPCX_GEOM_G(geom), K = (uint32_t)MPCX_GEOM_K(geom);
+  const uint32_t waves = (count + G - 1) / G;
   // a shared exponent's sliding-window schedule lives after the tables
   const bool use_sched = exp_shared && exp_bits > 0 && g_sched_width > 0;
-  const size_t sched_off = ws_words;
-  if (use_sched) ws_words += MPCX_SCHED_WORDS(32u * exp_words);
-  int rc = ensure_workspace(lane, ws_words * sizeof(uint32_t));
-  if (rc) return rc;
-  if (use_sched) {
-    mpcx::ExpSchedArgs sa{};
-    sa.exp = d_exps;
-    sa.exp_words = exp_words;
-    sa.max_width = (uint32_t)g_sched_width;
-    sa.sched = lane.ws + sched_off;
-    hipError_t e = mpcx_launch_expsched(&sa, st);
-    if (e != hipSuccess) return hip_fail(e, "launch k_expsched");
-  }
-  size_t ws_off = 0;
-  for (int i = 0; i < nparts; ++i) {
-    const Part& pt = parts[i];
-    const uint32_t G = (uint32_t)MPCX_GEOM_G(pt.geom), K = (uint32_t)MPCX_GEOM_K(pt.geom);
-    const uint32_t waves = (pt.count + G - 1) / G;
-    mpcx::ModexpArgs a{};
-    const uint32_t L = (uint32_t)MPCX_GEOM_L(pt.geom);
-    a.nd = dconst + mod->const_off[pt.geom];
-    a.r1d = a.nd + L;
-    a.r2d = a.nd + 2 * L;
-    a.base = d_bases + (size_t)pt.first * base_words;
-    a.exps = exp_shared ? d_exps : (d_exps ? d_exps + (size_t)pt.first * exp_words : nullptr);
-    a.mul = d_muls ? d_muls + (size_t)pt.first * mul_words : nullptr;
-    a.out = d_out + (size_t)pt.first * out_words;
-    a.table = lane.ws + ws_off;
-    a.count = pt.count;
-    a.base_words = base_words;
-    a.exp_words = exp_words;
-    a.mul_words = d_muls ? mul_words : 0;
-    a.exp_bits = exp_words ? exp_bits : 0;
-    // fixed window: 5 bits for per-operand exponents above 1024 bits (E/5 + 31
-    // table products < E/4 + 15 from 320 bits on; measured +2.4-2.6% on 2048- and
-    // 4096-bit exponents, profiles/r02/win_ab/), Go's 4 bits otherwise
-    a.win_bits = (!exp_shared && a.exp_bits > 1024u && g_fixed_win >= 5) ? 5u : 4u;
-    a.out_words = out_words;
-    a.n0inv = mod->n0inv;
-    a.exp_shared = exp_shared ? 1 : 0;
-    a.sched = use_sched ? lane.ws + sched_off : nullptr;
-    // the main geometries with the reduction on the matrix cores: the 4096-bit one
-    // (mx >= 1), the 2048-bit lane pair only on request (mx = 2: it measured slower,
-    // profiles/r05/mx/g5/)
-    const bool mx = g_mx && pt.geom == MPCX_MAIN_GEOM(mod->cls) && (pt.geom == 2 || (pt.geom == 5 && g_mx >= 2)) &&
-                    pt.count >= g_mx_min;
-    a.nwaves = waves;
-    if (mx) {
-      const uint8_t* t = nullptr;
-      if (int rc = mx_const(mod, di, &t)) return rc;
-      a.mx_img = t;
-    }
-    const char* kind = mx ? "modexp_mx" : "modexp";
-    const int ks = kstat_begin(lane);
-    hipError_t e = mpcx_launch_modexp(pt.geom, &a, waves, st);
-    if (e != hipSuccess) return hip_fail(e, "launch k_modexp");
-    g_devs[di].launches.fetch_add(1, std::memory_order_relaxed);
-    const double alg = alg_macs >= 0 ? alg_macs * pt.count / count : go_macs(mod->bits, a.exp_bits) * pt.count;
-    kstat_end(lane, ks, g_devs[di], di, kind, pt.geom, pt.count, alg);
-    launch_log(kind, pt.geom, pt.count, mod->bits, a.exp_bits, alg);
-    ws_off += (size_t)waves * MPCX_TABLE_ENTRIES * K * 64u;
-  }
+  const size_t sched_off = (size_t)waves * MPCX_TABLE_ENTRIES * K * 64u;
+  const size_t ws_words = sched_off + (use_sched ? MPCX_SCHED_WORDS(32u * exp_words) : 0);
+  if ((rc = ensure_workspace(lane, ws_words * sizeof(uint32_t)))) return rc;
+  uint32_t* sched = use_sched ? lane.ws + sched_off : nullptr;
+  if (use_sched && (rc = launch_expsched(d_exps, exp_words, sched, lane.st))) return rc;
+  const bool mx = runs_on_mx(geom, count, count, false);
+  const uint8_t* mx_img = nullptr;
+  if (mx && (rc = mx_const(mod, di, &mx_img))) return rc;
+  const mpcx::ModexpArgs a =
+      modexp_args(mod, geom, dconst, count, d_bases, base_words, d_exps, exp_words, d_muls, mul_words, d_out,
+                  out_words, lane.ws, exp_bits, exp_shared, sched, mx_img, waves);
+  const char* kind = mx ? "modexp_mx" : "modexp";
+  const int ks = kstat_begin(lane);
+  hipError_t e = mpcx_launch_modexp(geom, &a, waves, lane.st);
+  if (e != hipSuccess) return hip_fail(e, "launch k_modexp");
+  dev.launches.fetch_add(1, std::memory_order_relaxed);
+  const double alg = alg_macs >= 0 ? alg_macs : go_macs(mod->bits, a.exp_bits) * count;
+  kstat_end(lane, ks, dev, di, kind, geom, count, alg);
+  launch_log(kind, geom, count, mod->bits, a.exp_bits, alg);
   return MPCX_OK;
 }
 
@@ -1815,12 +1934,8 @@ static int modexp_host_range(int di, mpcx_mod_t mod, uint32_t count, const uint3
     return rc;
   const uint32_t rb = (uint32_t)MPCX_GEOM_RBITS(g_main_geom[mod->cls]);
   const bool ops_fit = host_ops_below(bases, count, base_words, rb) && host_ops_below(muls, count, mul_words, rb);
-  double alg = -1.0;
-  if (!exp_shared && exp_words) {  // the operands' own exponent lengths (launch log)
-    alg = 0.0;
-    for (uint32_t i = 0; i < count; ++i)
-      alg += go_macs(mod->bits, bit_length_words(exps + (size_t)i * exp_words, exp_words));
-  }
+  // the operands' own exponent lengths (launch log)
+  const double alg = !exp_shared && exp_words ? go_macs_sum(mod->bits, exps, exp_words, count) : -1.0;
   rc = modexp_enqueue(di, l, mod, count, (const uint32_t*)sg[0].ptr, base_words, (const uint32_t*)sg[1].ptr,
                       exp_words, exp_shared, exp_bits, muls ? (const uint32_t*)sg[3].ptr : nullptr, mul_words,
                       (uint32_t*)sg[2].ptr, out_words, ops_fit, alg);
@@ -1993,28 +2108,32 @@ int mpcx_modexp_multi_batch(uint32_t n_groups, const mpcx_modexp_group_t* gs) {
   if (!gs) return fail(MPCX_EINVAL, "null groups");
   const int n = ndev_or_fail();
   if (n < 0) return -n;
-  int cls = -1;
+  int cls = -1, rc;
   uint64_t total = 0;
+  uint32_t min_seg = 0xFFFFFFFFu;  // the smallest non-empty group
   for (uint32_t i = 0; i < n_groups; ++i) {
     const mpcx_modexp_group_t& g = gs[i];
     if (!g.mod) return fail(MPCX_EINVAL, "group %u: null modulus", i);
     if (cls < 0) cls = g.mod->cls;
     if (g.mod->cls != cls) return fail(MPCX_EINVAL, "group %u: modulus class differs from group 0's", i);
-    const uint32_t cw = (uint32_t)MPCX_CLASS_WORDS(cls);
-    if (g.count == 0) continue;
-    if (!g.bases || !g.out || (g.exp_words && !g.exps)) return fail(MPCX_EINVAL, "group %u: null buffer", i);
-    if (g.base_words == 0 || g.base_words > cw) return fail(MPCX_EINVAL, "group %u: base_words %u", i, g.base_words);
-    if (g.muls && (g.mul_words == 0 || g.mul_words > cw)) return fail(MPCX_EINVAL, "group %u: mul_words", i);
-    if (g.out_words < g.mod->words) return fail(MPCX_EINVAL, "group %u: out_words < modulus words", i);
+    if (g.count == 0) continue;  // an empty group is not checked
+    char pre[24];
+    std::snprintf(pre, sizeof pre, "group %u: ", i);
+    if ((rc = check_batch(pre, g.mod, g.count, g.bases, g.base_words, g.exps, g.exp_words, g.muls, g.mul_words, g.out,
+                          g.out_words)))
+      return rc;
     total += g.count;
+    min_seg = std::min(min_seg, g.count);
   }
   if (total == 0) return MPCX_OK;
   if (total > 0xFFFFFFFFull) return fail(MPCX_EINVAL, "too many operands");
   const int di = (int)(g_dev_rr.fetch_add(1, std::memory_order_relaxed) % (unsigned)n);
   Device& dev = g_devs[di];
-  int rc = bind(dev);
-  if (rc) return rc;
-  bool main_ok = true, forced_ok = true;  // every segment's modulus and operands fit the geometry
+  if ((rc = bind(dev))) return rc;
+  // every segment's modulus and operands fit the geometry; a forced geometry is
+  // tested with the operands rescanned against its own R (modexp_enqueue tests it
+  // with the scan against the main geometry's)
+  bool main_ok = true, forced_ok = true;
   {
     const int gf = g_force_geom >= 0 && MPCX_GEOM_CLASS(g_force_geom) == cls ? g_force_geom : -1;
     const uint32_t rb = (uint32_t)MPCX_GEOM_RBITS(g_main_geom[cls]);
@@ -2031,16 +2150,12 @@ int mpcx_modexp_multi_batch(uint32_t n_groups, const mpcx_modexp_group_t* gs) {
       }
     }
   }
-  bool mx_ok = g_mx && cls == 2 && total >= g_mx_min;  // the main geometry would run k_modexp_multi_mx
-  for (uint32_t i = 0; i < n_groups && mx_ok; ++i)
-    if (gs[i].count && gs[i].count < g_mx_seg_min) mx_ok = false;
+  // the model's mx input asks about the class's default main geometry (modexp_enqueue
+  // asks about the main geometry its batch would get)
+  const bool mx_ok = runs_on_mx(MPCX_MAIN_GEOM(cls), (uint32_t)total, min_seg, true);
   const int geom = choose_geom(dev, cls, (uint32_t)total, main_ok, forced_ok, mx_ok);
-  const uint32_t G = (uint32_t)MPCX_GEOM_G(geom), K = (uint32_t)MPCX_GEOM_K(geom), L = (uint32_t)MPCX_GEOM_L(geom);
-  // the 4096-bit main geometry's segments on the matrix cores when the launch is
-  // large and every segment fills at least one workgroup's worth of its tables
-  bool mx = g_mx && geom == MPCX_MAIN_GEOM(2) && total >= g_mx_min;
-  for (uint32_t i = 0; i < n_groups && mx; ++i)
-    if (gs[i].count && gs[i].count < g_mx_seg_min) mx = false;
+  const uint32_t G = (uint32_t)MPCX_GEOM_G(geom), K = (uint32_t)MPCX_GEOM_K(geom);
+  const bool mx = runs_on_mx(geom, (uint32_t)total, min_seg, true);
   // host-side layout of the packed inputs and outputs (words)
   struct Seg {
     uint32_t gi, waves, exp_bits;
@@ -2068,13 +2183,8 @@ int mpcx_modexp_multi_batch(uint32_t n_groups, const mpcx_modexp_group_t* gs) {
     sg.ws = ws_words;
     ws_words += (size_t)sg.waves * MPCX_TABLE_ENTRIES * K * 64u;
     sg.use_sched = g.exp_shared && sg.exp_bits > 0 && g_sched_width > 0;
-    if (g.exp_shared || !g.exp_words) {
-      sg.alg = go_macs(g.mod->bits, sg.exp_bits) * g.count;
-    } else {
-      sg.alg = 0.0;
-      for (uint32_t k = 0; k < g.count; ++k)
-        sg.alg += go_macs(g.mod->bits, bit_length_words(g.exps + (size_t)k * g.exp_words, g.exp_words));
-    }
+    sg.alg = g.exp_shared || !g.exp_words ? go_macs(g.mod->bits, sg.exp_bits) * g.count
+                                          : go_macs_sum(g.mod->bits, g.exps, g.exp_words, g.count);
     segs.push_back(sg);
   }
   for (auto& sg : segs)
@@ -2106,48 +2216,20 @@ int mpcx_modexp_multi_batch(uint32_t n_groups, const mpcx_modexp_group_t* gs) {
   }
   std::vector<mpcx::ModexpArgs> args(nseg);
   std::vector<uint32_t> first(nseg + 1, 0);
-  std::vector<const uint32_t*> dconst(nseg);
   for (size_t k = 0; k < nseg; ++k) {
     const Seg& sg = segs[k];
     const mpcx_modexp_group_t& g = gs[sg.gi];
-    if ((rc = mod_const(g.mod, di, &dconst[k]))) return rc;
-    if (sg.use_sched) {
-      mpcx::ExpSchedArgs sa{};
-      sa.exp = d_in + sg.in_e;
-      sa.exp_words = g.exp_words;
-      sa.max_width = (uint32_t)g_sched_width;
-      sa.sched = l.ws + sg.sched;
-      hipError_t e = mpcx_launch_expsched(&sa, l.st);
-      if (e != hipSuccess) return hip_fail(e, "launch k_expsched");
-    }
-    mpcx::ModexpArgs& a = args[k];
-    a.nd = dconst[k] + g.mod->const_off[geom];
-    a.r1d = a.nd + L;
-    a.r2d = a.nd + 2 * L;
-    a.base = d_in + sg.in_b;
-    a.exps = g.exp_words ? d_in + sg.in_e : nullptr;
-    a.mul = g.muls ? d_in + sg.in_m : nullptr;
-    a.out = d_out + sg.out_o;
-    a.table = l.ws + sg.ws;
-    a.count = g.count;
-    a.base_words = g.base_words;
-    a.exp_words = g.exp_words;
-    a.mul_words = g.muls ? g.mul_words : 0;
-    a.exp_bits = g.exp_words ? sg.exp_bits : 0;
-    a.win_bits = (!g.exp_shared && a.exp_bits > 1024u && g_fixed_win >= 5) ? 5u : 4u;
-    a.out_words = g.out_words;
-    a.n0inv = g.mod->n0inv;
-    a.exp_shared = g.exp_shared ? 1 : 0;
-    a.sched = sg.use_sched ? l.ws + sg.sched : nullptr;
-    if (mx) {
-      const uint8_t* t = nullptr;
-      if ((rc = mx_const(g.mod, di, &t))) return rc;
-      a.mx_img = t;
-      a.nwaves = sg.waves;
-      first[k + 1] = first[k] + (sg.waves + MX_WG - 1) / MX_WG;  // workgroups
-    } else {
-      first[k + 1] = first[k] + sg.waves;
-    }
+    const uint32_t* dconst = nullptr;
+    const uint8_t* mx_img = nullptr;
+    if ((rc = mod_const(g.mod, di, &dconst)) || (mx && (rc = mx_const(g.mod, di, &mx_img)))) return rc;
+    uint32_t* sched = sg.use_sched ? l.ws + sg.sched : nullptr;
+    if (sg.use_sched && (rc = launch_expsched(d_in + sg.in_e, g.exp_words, sched, l.st))) return rc;
+    args[k] = modexp_args(g.mod, geom, dconst, g.count, d_in + sg.in_b, g.base_words,
+                          g.exp_words ? d_in + sg.in_e : nullptr, g.exp_words, g.muls ? d_in + sg.in_m : nullptr,
+                          g.mul_words, d_out + sg.out_o, g.out_words, l.ws + sg.ws, sg.exp_bits, g.exp_shared, sched,
+                          mx_img, sg.waves);
+    // mx: each segment starts on a workgroup of MX_WG wavefronts (first[] counts workgroups)
+    first[k + 1] = first[k] + (mx ? (sg.waves + MX_WG - 1) / MX_WG : sg.waves);
   }
   if ((rc = h2d(l, l.stage[3].ptr, args.data(), seg_bytes)) ||
       (rc = h2d(l, (char*)l.stage[3].ptr + seg_bytes, first.data(), first_bytes)))
@@ -2158,17 +2240,11 @@ int mpcx_modexp_multi_batch(uint32_t n_groups, const mpcx_modexp_group_t* gs) {
                                           (uint32_t)nseg, first[nseg], mx ? 1 : 0, l.st);
   if (e != hipSuccess) return hip_fail(e, "launch k_modexp_multi");
   dev.launches.fetch_add(1, std::memory_order_relaxed);
-  {
-    double alg = 0.0;
-    uint32_t ops = 0;
-    for (const auto& sg : segs) {
-      alg += sg.alg;
-      ops += gs[sg.gi].count;
-    }
-    kstat_end(l, ks, dev, di, mx ? "modexp_multi_mx" : "modexp_multi", geom, ops, alg);
-  }
-  for (const auto& sg : segs)
-    launch_log(mx ? "modexp_multi_mx" : "modexp_multi", geom, gs[sg.gi].count, gs[sg.gi].mod->bits, sg.exp_bits, sg.alg);
+  const char* kind = mx ? "modexp_multi_mx" : "modexp_multi";
+  double alg = 0.0;
+  for (const auto& sg : segs) alg += sg.alg;
+  kstat_end(l, ks, dev, di, kind, geom, (uint32_t)total, alg);
+  for (const auto& sg : segs) launch_log(kind, geom, gs[sg.gi].count, gs[sg.gi].mod->bits, sg.exp_bits, sg.alg);
   for (const auto& sg : segs) {  // results straight into each group's buffer
     const mpcx_modexp_group_t& g = gs[sg.gi];
     if ((rc = d2h(l, g.out, d_out + sg.out_o, (size_t)g.count * g.out_words * 4))) return rc;
@@ -2642,123 +2718,60 @@ int mpcx_fixedbase_info(mpcx_fb_t fb, uint32_t* max_exp_bits, size_t* table_byte
 int mpcx_fixedbase_exp_batch(uint32_t nbases, const mpcx_fb_t* fbs, uint32_t count, const uint32_t* const* exps,
                              const uint32_t* exp_words, const uint32_t* muls, uint32_t mul_words, uint32_t* out,
                              uint32_t out_words) {
-  if (nbases == 0 || nbases > MPCX_FB_MAX_BASES) return fail(MPCX_EINVAL, "nbases %u outside [1, %d]", nbases, MPCX_FB_MAX_BASES);
-  if (!fbs || !exps || !exp_words) return fail(MPCX_EINVAL, "null argument");
-  for (uint32_t t = 0; t < nbases; ++t) {
-    if (!fbs[t]) return fail(MPCX_EINVAL, "null fixed base %u", t);
-    if (fbs[t]->mod != fbs[0]->mod) return fail(MPCX_EINVAL, "fixed bases of different moduli");
+  mpcx_fixedbase_group_t g{};  // the call as one group
+  g.nbases = nbases;
+  if (nbases >= 1 && nbases <= MPCX_FB_MAX_BASES) {  // otherwise fb_group_check fails before it reads the arrays
+    if (!fbs || !exps || !exp_words) return fail(MPCX_EINVAL, "null argument");
+    for (uint32_t t = 0; t < nbases; ++t) {
+      g.fbs[t] = fbs[t];
+      g.exps[t] = exps[t];
+      g.exp_words[t] = exp_words[t];
+    }
   }
-  mpcx_mod_t mod = fbs[0]->mod;
-  const uint32_t cw = (uint32_t)MPCX_CLASS_WORDS(mod->cls);
-  if (out_words < mod->words) return fail(MPCX_EINVAL, "out_words %u < modulus words %u", out_words, mod->words);
-  if (muls && (mul_words == 0 || mul_words > cw)) return fail(MPCX_EINVAL, "mul_words %u outside [1, %u]", mul_words, cw);
-  if (count == 0) return MPCX_OK;
-  if (!out) return fail(MPCX_EINVAL, "null output");
+  g.count = count;
+  g.muls = muls;
+  g.mul_words = mul_words;
+  g.out = out;
+  g.out_words = out_words;
   uint32_t nwin[MPCX_FB_MAX_BASES] = {0, 0};
-  for (uint32_t t = 0; t < nbases; ++t) {
-    if (exp_words[t] && !exps[t]) return fail(MPCX_EINVAL, "null exponents %u", t);
-    uint32_t bits = 0;
-    for (uint32_t i = 0; i < count && exp_words[t]; ++i)
-      bits = std::max(bits, bit_length_words(exps[t] + (size_t)i * exp_words[t], exp_words[t]));
-    const uint32_t wb = fbs[t]->wbits;
-    if (bits > fbs[t]->nwin * wb)
-      return fail(MPCX_EINVAL, "exponent of %u bits > fixed-base table's %u", bits, fbs[t]->nwin * wb);
-    nwin[t] = (bits + wb - 1) / wb;
-  }
+  if (int rc = fb_group_check(g, "", nwin)) return rc;
+  if (count == 0) return MPCX_OK;
   return run_sliced(count, g_split_min, [&](int di, uint32_t first, uint32_t n) {
-    const uint32_t* dconst = nullptr;
-    const uint32_t* dtab[MPCX_FB_MAX_BASES] = {nullptr, nullptr};
-    int rc;
-    if ((rc = mod_const(mod, di, &dconst))) return rc;
-    for (uint32_t t = 0; t < nbases; ++t)
-      if ((rc = fb_table(fbs[t], di, &dtab[t]))) return rc;
-    const size_t eb[MPCX_FB_MAX_BASES] = {(size_t)n * exp_words[0] * 4,
-                                          nbases > 1 ? (size_t)n * exp_words[1] * 4 : 0};
+    mpcx_fixedbase_group_t s = g;  // this device's slice
+    s.count = n;
+    for (uint32_t t = 0; t < nbases; ++t) s.exps[t] = g.exps[t] + (size_t)first * g.exp_words[t];
+    if (muls) s.muls = muls + (size_t)first * mul_words;
+    s.out = out + (size_t)first * out_words;
+    const size_t eb[MPCX_FB_MAX_BASES] = {(size_t)n * s.exp_words[0] * 4, (size_t)n * s.exp_words[1] * 4};
     const size_t ob = (size_t)n * out_words * 4, mb = muls ? (size_t)n * mul_words * 4 : 0;
     std::unique_lock<std::mutex> lk;
     Lane& l = acquire_lane(g_devs[di], lk);
     LaneDrain drain(l);
+    int rc;
     if ((rc = lane_stream(l))) return rc;
     Staging* sg = l.stage;
     if ((rc = ensure_buffer(sg[0], eb[0])) || (rc = ensure_buffer(sg[1], eb[1])) ||
         (rc = ensure_buffer(sg[2], ob)) || (muls && (rc = ensure_buffer(sg[3], mb))))
       return rc;
-    for (uint32_t t = 0; t < nbases; ++t)  // exps[t] exists only for t < nbases
-      if (eb[t] && (rc = h2d(l, sg[t].ptr, exps[t] + (size_t)first * exp_words[t], eb[t]))) return rc;
-    if (muls && (rc = h2d(l, sg[3].ptr, muls + (size_t)first * mul_words, mb))) return rc;
-    const int geom = fbs[0]->geom;
-    mpcx::FixedBaseArgs a{};
-    a.nd = dconst + mod->const_off[geom];
-    a.r1d = a.nd + MPCX_GEOM_L(geom);
-    a.r2d = a.nd + 2 * MPCX_GEOM_L(geom);
-    for (uint32_t t = 0; t < nbases; ++t) {
-      a.tables[t] = dtab[t];
-      a.exps[t] = (const uint32_t*)sg[t].ptr;
-      a.exp_words[t] = exp_words[t];
-      a.nwin[t] = nwin[t];
-      a.wbits[t] = fbs[t]->wbits;
-    }
-    a.nbases = nbases;
-    a.mul = muls ? (const uint32_t*)sg[3].ptr : nullptr;
-    a.mul_words = muls ? mul_words : 0;
-    a.out = (uint32_t*)sg[2].ptr;
-    a.out_words = out_words;
-    a.count = n;
-    a.n0inv = mod->n0inv;
+    for (uint32_t t = 0; t < nbases; ++t)
+      if (eb[t] && (rc = h2d(l, sg[t].ptr, s.exps[t], eb[t]))) return rc;
+    if (muls && (rc = h2d(l, sg[3].ptr, s.muls, mb))) return rc;
+    const int geom = s.fbs[0]->geom;
+    const uint32_t* d_exps[MPCX_FB_MAX_BASES] = {(const uint32_t*)sg[0].ptr, (const uint32_t*)sg[1].ptr};
+    mpcx::FixedBaseArgs a;
+    if ((rc = fixedbase_args(s, geom, di, nwin, d_exps, (const uint32_t*)sg[3].ptr, (uint32_t*)sg[2].ptr, &a)))
+      return rc;
     const uint32_t blocks = (n + MPCX_GEOM_G(geom) - 1) / MPCX_GEOM_G(geom);
     const uint32_t split = fb_split_for(g_devs[di], blocks);
     const int ks = kstat_begin(l);
     hipError_t e = launch_fixedbase(geom, &a, blocks, split, l.st);
     if (e != hipSuccess) return hip_fail(e, "launch k_fixedbase");
     g_devs[di].launches.fetch_add(1, std::memory_order_relaxed);
-    {
-      // Go-equivalent (launch log): one Exp per base per operand; executed
-      // (kernel stats): one product per window of each exponent, plus
-      // the multiplier's, 2 L^2 MACs each
-      double alg = 0.0, exec = 0.0;
-      const double l2 = 2.0 * (double)((mod->bits + 31) / 32) * (double)((mod->bits + 31) / 32);
-      uint32_t eb_max = 0;
-      for (uint32_t t = 0; t < nbases; ++t)
-        for (uint32_t i = 0; i < n && exp_words[t]; ++i) {
-          const uint32_t b = bit_length_words(exps[t] + (size_t)(first + i) * exp_words[t], exp_words[t]);
-          alg += go_macs(mod->bits, b);
-          exec += (double)((b + fbs[t]->wbits - 1) / fbs[t]->wbits) * l2;
-          eb_max = std::max(eb_max, b);
-        }
-      if (muls) exec += (double)n * l2;
-      kstat_end(l, ks, g_devs[di], di, "fixedbase", geom, n, exec);
-      launch_log("fixedbase", geom, n, mod->bits, eb_max, alg);
-    }
-    return d2h_sync(out + (size_t)first * out_words, sg[2].ptr, ob, l);
+    const FbWork w = fb_group_work(s);
+    kstat_end(l, ks, g_devs[di], di, "fixedbase", geom, n, w.exec);
+    launch_log("fixedbase", geom, n, s.fbs[0]->mod->bits, w.eb_max, w.alg);
+    return d2h_sync(s.out, sg[2].ptr, ob, l);
   });
-}
-
-// One comb group's checks (mpcx_fixedbase_exp_batch's rules) and the windows
-// its launch processes per base (the longest exponent's).
-static int fb_group_check(const mpcx_fixedbase_group_t& g, uint32_t gi, uint32_t* nwin) {
-  if (g.nbases == 0 || g.nbases > MPCX_FB_MAX_BASES)
-    return fail(MPCX_EINVAL, "group %u: nbases %u outside [1, %d]", gi, g.nbases, MPCX_FB_MAX_BASES);
-  for (uint32_t t = 0; t < g.nbases; ++t) {
-    if (!g.fbs[t]) return fail(MPCX_EINVAL, "group %u: null fixed base %u", gi, t);
-    if (g.fbs[t]->mod != g.fbs[0]->mod) return fail(MPCX_EINVAL, "group %u: fixed bases of different moduli", gi);
-  }
-  mpcx_mod_t mod = g.fbs[0]->mod;
-  const uint32_t cw = (uint32_t)MPCX_CLASS_WORDS(mod->cls);
-  if (g.out_words < mod->words) return fail(MPCX_EINVAL, "group %u: out_words < modulus words", gi);
-  if (g.muls && (g.mul_words == 0 || g.mul_words > cw)) return fail(MPCX_EINVAL, "group %u: mul_words", gi);
-  if (g.count == 0) return MPCX_OK;  // an empty group's buffers may be null
-  if (!g.out) return fail(MPCX_EINVAL, "group %u: null output", gi);
-  for (uint32_t t = 0; t < g.nbases; ++t) {
-    if (g.exp_words[t] && !g.exps[t]) return fail(MPCX_EINVAL, "group %u: null exponents %u", gi, t);
-    uint32_t bits = 0;
-    for (uint32_t i = 0; i < g.count && g.exp_words[t]; ++i)
-      bits = std::max(bits, bit_length_words(g.exps[t] + (size_t)i * g.exp_words[t], g.exp_words[t]));
-    const uint32_t wb = g.fbs[t]->wbits;
-    if (bits > g.fbs[t]->nwin * wb)
-      return fail(MPCX_EINVAL, "group %u: exponent of %u bits > fixed-base table's %u", gi, bits, g.fbs[t]->nwin * wb);
-    nwin[t] = (bits + wb - 1) / wb;
-  }
-  return MPCX_OK;
 }
 
 int mpcx_fixedbase_multi_batch(uint32_t n_groups, const mpcx_fixedbase_group_t* gs) {
@@ -2770,7 +2783,9 @@ int mpcx_fixedbase_multi_batch(uint32_t n_groups, const mpcx_fixedbase_group_t* 
   uint64_t total = 0;
   std::vector<uint32_t> nwin((size_t)n_groups * MPCX_FB_MAX_BASES, 0);
   for (uint32_t i = 0; i < n_groups; ++i) {
-    if ((rc = fb_group_check(gs[i], i, &nwin[(size_t)i * MPCX_FB_MAX_BASES]))) return rc;
+    char pre[24];
+    std::snprintf(pre, sizeof pre, "group %u: ", i);
+    if ((rc = fb_group_check(gs[i], pre, &nwin[(size_t)i * MPCX_FB_MAX_BASES]))) return rc;
     const int c = gs[i].fbs[0]->mod->cls;
     if (cls < 0) cls = c;
     if (c != cls) return fail(MPCX_EINVAL, "group %u: modulus class differs from group 0's", i);
@@ -2788,7 +2803,7 @@ int mpcx_fixedbase_multi_batch(uint32_t n_groups, const mpcx_fixedbase_group_t* 
     if (geom < 0) geom = g;
     if (g != geom) return fail(MPCX_EINVAL, "group %u: comb table layout differs from group 0's", i);
   }
-  const uint32_t G = (uint32_t)MPCX_GEOM_G(geom), L = (uint32_t)MPCX_GEOM_L(geom);
+  const uint32_t G = (uint32_t)MPCX_GEOM_G(geom);
   struct Seg {
     uint32_t gi, waves;
     size_t in_e[MPCX_FB_MAX_BASES], in_m, out_o;
@@ -2827,32 +2842,13 @@ int mpcx_fixedbase_multi_batch(uint32_t n_groups, const mpcx_fixedbase_group_t* 
   for (size_t k = 0; k < nseg; ++k) {
     const Seg& sg = segs[k];
     const mpcx_fixedbase_group_t& g = gs[sg.gi];
-    mpcx_mod_t mod = g.fbs[0]->mod;
     for (uint32_t t = 0; t < g.nbases; ++t)
       if ((rc = h2d(l, d_in + sg.in_e[t], g.exps[t], (size_t)g.count * g.exp_words[t] * 4))) return rc;
     if (g.muls && (rc = h2d(l, d_in + sg.in_m, g.muls, (size_t)g.count * g.mul_words * 4))) return rc;
-    const uint32_t* dconst = nullptr;
-    if ((rc = mod_const(mod, di, &dconst))) return rc;
-    mpcx::FixedBaseArgs& a = args[k];
-    a.nd = dconst + mod->const_off[geom];
-    a.r1d = a.nd + L;
-    a.r2d = a.nd + 2 * L;
-    for (uint32_t t = 0; t < g.nbases; ++t) {
-      const uint32_t* dt = nullptr;
-      if ((rc = fb_table(g.fbs[t], di, &dt))) return rc;
-      a.tables[t] = dt;
-      a.exps[t] = d_in + sg.in_e[t];
-      a.exp_words[t] = g.exp_words[t];
-      a.nwin[t] = nwin[(size_t)sg.gi * MPCX_FB_MAX_BASES + t];
-      a.wbits[t] = g.fbs[t]->wbits;
-    }
-    a.nbases = g.nbases;
-    a.mul = g.muls ? d_in + sg.in_m : nullptr;
-    a.mul_words = g.muls ? g.mul_words : 0;
-    a.out = d_out + sg.out_o;
-    a.out_words = g.out_words;
-    a.count = g.count;
-    a.n0inv = mod->n0inv;
+    const uint32_t* d_exps[MPCX_FB_MAX_BASES] = {d_in + sg.in_e[0], d_in + sg.in_e[1]};
+    if ((rc = fixedbase_args(g, geom, di, &nwin[(size_t)sg.gi * MPCX_FB_MAX_BASES], d_exps, d_in + sg.in_m,
+                             d_out + sg.out_o, &args[k])))
+      return rc;
     first[k + 1] = first[k] + sg.waves;
   }
   if ((rc = h2d(l, l.stage[3].ptr, args.data(), seg_bytes)) ||
@@ -2865,32 +2861,14 @@ int mpcx_fixedbase_multi_batch(uint32_t n_groups, const mpcx_fixedbase_group_t* 
                                         fb_split_for(dev, first[nseg]), l.st);
   if (e != hipSuccess) return hip_fail(e, "launch k_fixedbase_multi");
   dev.launches.fetch_add(1, std::memory_order_relaxed);
-  {
-    // as mpcx_fixedbase_exp_batch: Go-equivalent work per base exponent (launch
-    // log), executed products x 2 L^2 (kernel stats)
-    double alg_all = 0.0, exec = 0.0;
-    uint32_t ops = 0;
-    for (const auto& sg : segs) {
-      const mpcx_fixedbase_group_t& g = gs[sg.gi];
-      mpcx_mod_t mod = g.fbs[0]->mod;
-      const double l2 = 2.0 * (double)((mod->bits + 31) / 32) * (double)((mod->bits + 31) / 32);
-      double alg = 0.0;
-      uint32_t eb_max = 0;
-      for (uint32_t t = 0; t < g.nbases; ++t)
-        for (uint32_t i = 0; i < g.count && g.exp_words[t]; ++i) {
-          const uint32_t b = bit_length_words(g.exps[t] + (size_t)i * g.exp_words[t], g.exp_words[t]);
-          alg += go_macs(mod->bits, b);
-          exec += (double)((b + g.fbs[t]->wbits - 1) / g.fbs[t]->wbits) * l2;
-          eb_max = std::max(eb_max, b);
-        }
-      if (g.muls) exec += (double)g.count * l2;
-      launch_log("fixedbase_multi", geom, g.count, mod->bits, eb_max, alg);
-      alg_all += alg;
-      ops += g.count;
-    }
-    (void)alg_all;
-    kstat_end(l, ks, dev, di, "fixedbase_multi", geom, ops, exec);
+  double exec = 0.0;
+  for (const auto& sg : segs) {
+    const mpcx_fixedbase_group_t& g = gs[sg.gi];
+    const FbWork w = fb_group_work(g);
+    launch_log("fixedbase_multi", geom, g.count, g.fbs[0]->mod->bits, w.eb_max, w.alg);
+    exec += w.exec;
   }
+  kstat_end(l, ks, dev, di, "fixedbase_multi", geom, (uint32_t)total, exec);
   for (const auto& sg : segs) {  // results straight into each group's buffer
     const mpcx_fixedbase_group_t& g = gs[sg.gi];
     if ((rc = d2h(l, g.out, d_out + sg.out_o, (size_t)g.count * g.out_words * 4))) return rc;

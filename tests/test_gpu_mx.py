@@ -237,3 +237,49 @@ def test_mx_ragged_batch_unreduced_operands(dev):
     assert _mx_launched(st)
     for i in [0, 1, 2, count - 1] + rng.sample(range(3, count - 1), 20):
         assert got[i] == pow(bases[i], exps[i], m), i
+
+
+_PLAN_KINDS = {"modexp": False, "modexp_multi": False, "modexp_mx": True, "modexp_multi_mx": True}
+
+
+def _plan(stats):
+    # {(geometry, ran on the matrix cores)} of the modexp launches since the last reset
+    return {(k["geom"], _PLAN_KINDS[k["kind"]]) for k in stats["kernels"]
+            if k.get("kind") in _PLAN_KINDS and k.get("launches", 0) > 0}
+
+
+def test_one_group_multi_plans_like_single(dev, paillier_key):
+    """At default options a batch takes the same geometry, and the same choice
+    between the matrix cores and the VALU kernel, through mpcx_modexp_batch and as
+    the only group of mpcx_modexp_multi_batch. The counts bracket mx_seg_min (64),
+    mx_min (2048) and the launch-time model's narrow / mid / main crossovers."""
+    rng = random.Random(5110)
+    m = paillier_key["N"] ** 2  # the 4096-bit class: N^2 of the 2048-bit golden key
+    e = rng.getrandbits(40) | (1 << 39)  # a short shared exponent: milliseconds per case
+    saved = {k: mpcx.get_option(k) for k in ("mx", "geom_policy")}
+    mod = mpcx.Modulus(m)
+    try:
+        mpcx.set_option("mx", 1)
+        mpcx.set_option("geom_policy", 1)
+        mpcx.set_option("force_geom", -1)
+        for count in (1, 63, 64, 1250, 2047, 2048, 5000):
+            bases = [rng.randrange(m) for _ in range(count)]
+            want = [pow(x, e, m) for x in bases]
+            mpcx.kernel_stats(reset=True)
+            single = mod.exp(bases, e)
+            st_single = mpcx.kernel_stats()
+            mpcx.kernel_stats(reset=True)
+            multi = mpcx.modexp_multi([(mod, bases, e, None)])[0]
+            st_multi = mpcx.kernel_stats()
+            assert single == want, count
+            assert multi == want, count
+            p1, p2 = _plan(st_single), _plan(st_multi)
+            assert len(p1) == 1 and len(p2) == 1, (count, st_single, st_multi)
+            (g1, mx1), (g2, mx2) = next(iter(p1)), next(iter(p2))
+            assert g1 == g2, (count, g1, g2)
+            assert mx1 == mx2, (count, mx1, mx2)
+    finally:
+        mod.release()
+        for k, v in saved.items():
+            mpcx.set_option(k, v)
+        mpcx.set_option("force_geom", -1)
