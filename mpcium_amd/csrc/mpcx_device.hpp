@@ -41,26 +41,18 @@
 
 #include "mpcx_internal.h"
 
-#ifndef MPCX_SCHED_BARRIER
-#define MPCX_SCHED_BARRIER 0
+#if defined(MX_EMIT) || defined(MX_ITER_FENCE) || defined(MX_SPLIT_MAD) || defined(MX_READ_FENCE) ||          \
+    defined(MX_PRIO) || defined(MX_PRIO_P) || defined(MX_PRIO_F) || defined(MX_PRIO_R) || defined(MX_PRIO_R2) || \
+    defined(MX_PRIO_C) || defined(MX_CARRY_SKIP) || defined(MPCX_SCHED_BARRIER) || defined(MPCX_SQR_OPT) ||      \
+    defined(MPCX_PREFETCH_B) || defined(MPCX_SQR_B2) || defined(MPCX_PRIME2C_DBL_FOLD)
+#error "retired A/B switch; see DESIGN.md 5.2g"
 #endif
-#ifndef MPCX_SQR_OPT
-#define MPCX_SQR_OPT 1  // half-product squarings (montmul<..., true>)
-#endif
+
 #ifndef MPCX_PREFETCH2_KMAX
 #define MPCX_PREFETCH2_KMAX 24  // montmul reads b two digits ahead for K below this
 #endif
-#ifndef MPCX_PREFETCH_B
-#define MPCX_PREFETCH_B 1
-#endif
-#ifndef MPCX_SQR_B2
-#define MPCX_SQR_B2 1  // k_modexp / k_prime2c squarings read 2*b from LDS (no per-iteration doubling)
-#endif
 #ifndef MPCX_BLOCK_FENCE
-#define MPCX_BLOCK_FENCE 0  // scheduling fence between montmul's P blocks (1: all, 2: K >= 16; the prime kernels' TU sets 1)
-#endif
-#ifndef MPCX_PRIME2C_DBL_FOLD
-#define MPCX_PRIME2C_DBL_FOLD 1  // k_prime2c: the square-and-double step as one product with B = 2^bit x
+#define MPCX_BLOCK_FENCE 0  // 1: scheduling fence between montmul's P blocks (the prime kernels' TU sets it)
 #endif
 #ifndef MPCX_WAVES_PER_EU_FERMAT
 #define MPCX_WAVES_PER_EU_FERMAT 1
@@ -170,10 +162,19 @@ __device__ __forceinline__ void carry_pass32(uint32_t (&d)[K]) {
 
 // A <- A * B * R^-1 (almost Montgomery, result < 2N given A, B < 2N), with
 // B's L digits in LDS at bl[0..L) (p = this lane's index in its group).
-// Result digits are <= 2^28 + 2^8 (two carry passes at the end), which keeps
-// every product below 2^56.01 (2^57.02 for the doubled squaring products);
-// each accumulator register restarts every K iterations (see the end of the
-// block loop), so it stays below 2^63 with no carry pass inside the product.
+// Digits: A's and B's are accepted in [0, 2^28 + 2^16): montmul's own results
+// (<= 2^28 + 2^8, below) and montmul_mx's (< 2^28 + 2^16, mpcx_mx.hpp); N's are
+// canonical and m_i < 2^28. For K <= 37:
+//  * a product a*b is < 2^56.001, a squaring's doubled a*(2b) < 2^57.001, and
+//    with k_prime2c's B = 2^bit x (its digits are montmul's own, doubled twice)
+//    a*(4b) < 2^58.001; m_i*N is < 2^56;
+//  * an accumulator register restarts every K iterations (see the end of the
+//    block loop). In between it takes K products a*b and K products m_i*N, or
+//    for a squaring (K + 1) / 2 doubled products and K products m_i*N, plus a
+//    < 2^35 fold per iteration: < 37 * 2^57.001 + 2^41 < 2^62.3, squaring
+//    < 19 * 2^58.001 + 37 * 2^56 + 2^41 < 2^62.9. No carry pass inside the
+//    product;
+//  * the two carry passes at the end leave < 2^28 + 2^35, then <= 2^28 + 2^8.
 //
 // SQR (B == A, squaring): each unordered digit pair {i, j} needs ONE product
 // 2*a_i*a_j (plus a_i^2 on the diagonal). In iteration t the product of
@@ -237,15 +238,10 @@ __device__ __forceinline__ void montmul(uint32_t (&A)[K], const uint32_t* bl, co
       ab(std::integral_constant<int, 0>{});
       uint32_t m = ((uint32_t)acc[u] * n0inv) & M28;
       if constexpr (P > 1) m = group_bcast<P>(m, m_src_addr);
-#if MPCX_PREFETCH_B
       // next digit of b, in flight behind the bpermute and the a*b_i mads
       // (the last read of the last block touches the neighbour row: unused)
       if constexpr (!PF2) bnext = bo[u + 1];
-#endif
       static_for<1, K>(ab);
-#if !MPCX_PREFETCH_B
-      if constexpr (!PF2) bnext = bo[u + 1];
-#endif
       static_for<0, K>([&](auto kc) {
         constexpr int k = decltype(kc)::value;
         mad64(acc[(k + u) % K], m, Nd[k]);
@@ -257,26 +253,18 @@ __device__ __forceinline__ void montmul(uint32_t (&A)[K], const uint32_t* bl, co
       } else {
         acc[u] = 0;
       }
-#if MPCX_SCHED_BARRIER
-      // keep iterations from being interleaved by the machine scheduler: it
-      // otherwise hoists b loads and mads across iterations and blows the
-      // register budget (occupancy) for no issue-rate gain
-      __builtin_amdgcn_sched_barrier(0);
-#endif
     });
     // No mid-way carry pass is needed: a register is reset (slot 0 retires to
-    // a 28-bit value) once every K iterations, so it sums at most K iterations
-    // of one a*b and one m*N product (< 2^58.02 + 2^56 for the doubled
-    // squaring row of k_prime2c, whose digits reach 2^30.01) plus a < 2^35
-    // fold: < 2^62.8 for K <= 37. profiles/r03/kernel_ab: dropping the pass
-    // took the config-2 kernel from 176.3 to 171.7 ms.
+    // a 28-bit value) once every K iterations, so it stays below 2^62.9 for
+    // K <= 37 (the bounds above montmul). profiles/r03/kernel_ab: dropping the
+    // pass took the config-2 kernel from 176.3 to 171.7 ms.
     // block boundary as a scheduling fence (mpcx_prime.hip: without it
     // k_prime2c's live ranges grew past its 3-wave budget and spilled; the
-    // k_modexp geometries fit better without it). 2: long blocks only (K >= 16).
-    if constexpr (MPCX_BLOCK_FENCE == 1 || (MPCX_BLOCK_FENCE == 2 && K >= 16)) __builtin_amdgcn_sched_barrier(0);
+    // k_modexp geometries fit better without it).
+    if constexpr (MPCX_BLOCK_FENCE == 1) __builtin_amdgcn_sched_barrier(0);
   }
   carry_pass64<P, K>(acc);
-  // digits are now < 2^28 + 2^37: one more pass brings them to <= 2^28 + 2^10
+  // digits are now < 2^28 + 2^35: one more pass brings them to <= 2^28 + 2^8
   const uint32_t ctop = (uint32_t)(acc[K - 1] >> DB);
 #pragma unroll
   for (int k = K - 1; k >= 1; --k) A[k] = ((uint32_t)acc[k] & M28) + (uint32_t)(acc[k - 1] >> DB);
@@ -302,11 +290,12 @@ __device__ __forceinline__ void lds_store_digits(uint32_t* bl, int p, const uint
   for (int k = 0; k < K; ++k) bl[p * K + k] = A[k];
 }
 
-// the squaring's multiplier row: 2*A when montmul reads it as B2IN, else A
+// the squaring's multiplier row: 2*A, which montmul reads as B2IN (no
+// per-iteration doubling)
 template <int K>
 __device__ __forceinline__ void lds_store_sqr(uint32_t* bl, int p, const uint32_t (&A)[K]) {
 #pragma unroll
-  for (int k = 0; k < K; ++k) bl[p * K + k] = MPCX_SQR_B2 ? A[k] << 1 : A[k];
+  for (int k = 0; k < K; ++k) bl[p * K + k] = A[k] << 1;
 }
 
 // bits [wb*j, wb*j + wb) of the ew-word exponent e (wb <= 32; bits past the
@@ -585,12 +574,12 @@ __device__ __forceinline__ void modexp_wave(const ModexpArgs& a, const uint32_t 
       }
       if (st == ST_FIN) break;  // the exit product runs after the loop (m's digits live only there)
       if (sqr) {
-        montmul_mx<S, true, (bool)MPCX_SQR_B2>(A, lds, mx_md, mxc, lane);
+        montmul_mx<S, true, true>(A, lds, mx_md, mxc, lane);
       } else {
         montmul_mx<S, false, false>(A, lds, mx_md, mxc, lane);
       }
-    } else if (MPCX_SQR_OPT && sqr) {
-      montmul<P, K, true, (bool)MPCX_SQR_B2>(A, bl, Nd, a.n0inv, m_src_addr, p);
+    } else if (sqr) {
+      montmul<P, K, true, true>(A, bl, Nd, a.n0inv, m_src_addr, p);
     } else {
       montmul<P, K, false>(A, bl, Nd, a.n0inv, m_src_addr, p);
     }
@@ -1509,7 +1498,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
       for (int k = 0; k < K; ++k) one[k] = (p == 0 && k == 0) ? 1u : 0u;
       lds_store_digits<K>(sv, p, A);
       lds_store_digits<K>(bl, p, one);
-    } else if (MPCX_PRIME2C_DBL_FOLD && st == SQ) {
+    } else if (st == SQ) {
       // x <- 2^bit x^2 as ONE squaring product: B = 2^bit x in LDS, x in
       // registers -- the half-product schedule then sums x_i (2 x_j) pairs
       // (digits of B < 2^29 + 2^11, b2 < 2^31: the schedule's bounds hold, and
@@ -1518,22 +1507,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
       const uint32_t dsh = (jb > 0 && jb < nbits && word_bit(nw, jb)) ? 1u : 0u;
       uint32_t B2[K];
 #pragma unroll
-      for (int k = 0; k < K; ++k) B2[k] = A[k] << (dsh + (MPCX_SQR_B2 ? 1u : 0u));  // montmul reads 2B
+      for (int k = 0; k < K; ++k) B2[k] = A[k] << (dsh + 1u);  // montmul reads 2B
       lds_store_digits<K>(bl, p, B2);
     } else {
-      lds_store_sqr<K>(bl, p, A);  // SS (or SQ without the fold): a plain squaring
+      lds_store_sqr<K>(bl, p, A);  // SS: a plain squaring
     }
     wave_lds_fence();
     if (st == EX) {
       montmul<P, K, false>(A, bl, Nd, n0inv, 0, p);
     } else {
-      montmul<P, K, true, (bool)MPCX_SQR_B2>(A, bl, Nd, n0inv, 0, p);
+      montmul<P, K, true, true>(A, bl, Nd, n0inv, 0, p);
     }
     if (st == SQ) {
-      if (!MPCX_PRIME2C_DBL_FOLD) {
-        const int jb = i + sh;  // bit jb of n - 1: bit jb of n except bit 0 (n odd)
-        double_digits<P, K>(A, jb > 0 && jb < nbits && word_bit(nw, jb));
-      }
       if (--i < 0) st = EX;
     } else if (st == SS) {
       st = EX;

@@ -76,14 +76,10 @@ __device__ __forceinline__ uint32_t mx_spread7(uint32_t x) {
 // the m_i N half: T's low L digits are emitted to tl[] as the window passes them
 // (lane p == 0 of the group), the high L digits end in A (<= 2^28 + 2^10).
 //
-// Emission (MX_EMIT): 0 = lane p == 0 stores under an exec mask (two exec writes
-// per iteration, and the SALU mask ops serialise against the MADs' carry-out
-// SGPRs); 1 = every lane stores, lanes p != 0 into a per-lane trash slot of the
-// wave's LDS area (tr: that lane's slots, L words from lane + 0), so the loop
-// body has no exec changes.
-#ifndef MX_EMIT
-#define MX_EMIT 1
-#endif
+// Every lane stores, lanes p != 0 into a per-lane trash slot of the wave's LDS
+// area (tr: that lane's slots, L words from lane + 0), so that the loop body has
+// no exec-mask changes (their SALU mask ops serialise against the MADs' carry-out
+// SGPRs).
 template <int P, int K, bool SQR, bool B2IN>
 __device__ __forceinline__ void mx_product(uint32_t (&A)[K], const uint32_t* bl, uint32_t* tl, uint32_t* tr, int p) {
   static_assert(!SQR || (K % 2) == 1, "squaring schedule needs an odd digit count per lane");
@@ -94,7 +90,7 @@ __device__ __forceinline__ void mx_product(uint32_t (&A)[K], const uint32_t* bl,
 #pragma nounroll
   for (int o = 0; o < P; ++o) {
     const uint32_t* bo = bl + o * K;
-    uint32_t* to = ((MX_EMIT == 0 || p == 0) ? tl : tr) + o * K;
+    uint32_t* to = (p == 0 ? tl : tr) + o * K;
     const uint32_t dsh = p > o ? 0u : (p == o ? 1u : 31u);
     static_for<0, K>([&](auto uc) {
       constexpr int u = decltype(uc)::value;
@@ -120,16 +116,8 @@ __device__ __forceinline__ void mx_product(uint32_t (&A)[K], const uint32_t* bl,
       // lane 0's digit leaves the window as T's digit i (in CIOS it is zero);
       // it must not shift into the previous group's top slot
       const uint32_t lo = (uint32_t)a0 & M28;
-      if constexpr (MX_EMIT == 1) {
-        to[u] = lo;
-      } else {
-        if (p == 0) to[u] = lo;
-      }
+      to[u] = lo;
       acc[u] = from_next_lane(p == 0 ? 0u : lo);
-#ifndef MX_ITER_FENCE
-#define MX_ITER_FENCE 0
-#endif
-      if constexpr (MX_ITER_FENCE) __builtin_amdgcn_sched_barrier(0);
     });
   }
   carry_pass64<P, K>(acc);
@@ -145,22 +133,12 @@ __device__ __forceinline__ int mx_from_prev_quarter(int v, int lane) {
   return __builtin_amdgcn_ds_bpermute(((lane - 16) & 63) << 2, v);
 }
 
-// split of the radix-2^28 digit sum c0 + c1 2^7 + c2 2^14 + c3 2^21 (+ add) into
-// lo (bits 0..27 of the sum, as a signed remainder of lo_sum) and the carry:
-// lo_sum = the low parts (< 2^31 for the bounds above), hi_sum = the high parts
-__device__ __forceinline__ void mx_split(const mx_v4i c, int add, int& lo_sum, int& hi_sum) {
-  lo_sum = c[0] + ((c[1] & 0x1FFFFF) << 7) + ((c[2] & 0x3FFF) << 14) + ((c[3] & 0x7F) << 21) + add;
-  hi_sum = (c[1] >> 21) + (c[2] >> 14) + (c[3] >> 7);
-}
-
-// MX_SPLIT_MAD: the same digit sum as one 64-bit value V = c0 + add + c1 2^7 +
-// c2 2^14 + c3 2^21 built by three v_mad_i64_i32 (the MAD pipe idles during the
-// reduction) instead of masks, shifts and adds on the VALU; lo = V mod 2^28 and
-// the carry V >> 28 (arithmetic) follow from V directly. Multipliers in SGPRs
-// (VOP3 takes no literal), so the compiler cannot turn them back into shifts.
-#ifndef MX_SPLIT_MAD
-#define MX_SPLIT_MAD 1
-#endif
+// the radix-2^28 digit sum of four column sums as one 64-bit value V = c0 + add +
+// c1 2^7 + c2 2^14 + c3 2^21, built by three v_mad_i64_i32 (the MAD pipe idles
+// during the reduction) instead of masks, shifts and adds on the VALU; the digit
+// V mod 2^28 and the carry V >> 28 (arithmetic) follow from V directly.
+// Multipliers in SGPRs (VOP3 takes no literal), so the compiler cannot turn them
+// back into shifts.
 __device__ __forceinline__ int64_t mx_sum64(const mx_v4i c, int add) {
   int64_t v = (int64_t)(c[0] + add);
   uint64_t cy;
@@ -194,10 +172,7 @@ __device__ __forceinline__ void mx_toeplitz(mx_v4i (&acc)[O1 - O0], const uint8_
     if constexpr (j + 1 <= JHI) fnext = ld(j + 1);
     // the next block's read stays one block ahead: ALU and MFMA may move
     // across, LDS reads may not (hoisting them all costs 4 VGPRs per block)
-#ifndef MX_READ_FENCE
-#define MX_READ_FENCE 1
-#endif
-    if constexpr (MX_READ_FENCE) __builtin_amdgcn_sched_barrier(0x000F);
+    __builtin_amdgcn_sched_barrier(0x000F);
     static_for<0, S::KB>([&](auto kc) {
       constexpr int kb = decltype(kc)::value;
       constexpr int o = j + 4 * kb;
@@ -221,6 +196,10 @@ __device__ __forceinline__ mx_v4i mx_transpose4(uint32_t x0, uint32_t x1, uint32
 // wave's product loop with its SIMD partner's reduction (slower), and each chunk's
 // normalisation interleaved with the next chunk's MFMAs (equal).
 // A <- A * B * R^-1 + m (mod-m class preserved; result in (m/2, 3m/2) for A, B < 2m).
+// Postcondition: every digit of A is in [0, 2^28 + 2^16). The reduction emits
+// digits in (-2^16, 2^28 + 2^16) and the signed carry passes at the end run only
+// while some digit of the wave is negative; mx_product and montmul take such
+// digits as they are (bounds above montmul, mpcx_device.hpp).
 // rows: this wavefront's G operand rows (S::ROW words each); operand g's row holds
 // B (2B for squarings) on entry and is the scratch of the whole product: T's low
 // digits overwrite B as the loop consumes it, then T's high digits + m, then
@@ -259,43 +238,21 @@ __device__ __forceinline__ void montmul_mx(uint32_t (&A)[S::K], uint32_t* rows, 
 #ifndef MPCX_MX_TIMING
 #define MPCX_MX_TIMING 0  // microbench builds only: 1 = product loop alone, 2 = reduction alone
 #endif
-  // MX_PRIO, the wave's issue priority by phase of the Montgomery product
-  // (s_setprio; the two waves of a SIMD are mostly in different phases):
-  // product loop P, fragment build F, q products R, q m products R2, carry
-  // passes C. Presets: 0 none; 1 R = 1 (138.7 vs 139.6 ms, profiles/r06/libab1);
-  // 2 P = 1; 3 P = F = 1; 4 P 2 > F = R = R2 1 > C 0; 5 (default) P 3 > F 2 >
-  // R 1 > R2 = C 0. Config 2, three interleaved rounds per A/B
-  // (profiles/r06/prioab2..4): 1 133.5 -> 4 128.2 (2, 3: 129.1) -> 5 123.3 ms.
-  // The levels must fall along the product: equal levels for P and F (126.5) or
-  // for R and R2 (124.9) lose, and so does the product loop's second half one
-  // level down (126.0-126.6 vs 125.2, prioab5). Whenever the two waves are in
-  // different phases, the one that is earlier in its product issues first; the
-  // other fills the slots it leaves (a product-loop wave alone issues a MAD only
-  // every ~10 cycles).
-#ifndef MX_PRIO
-#define MX_PRIO 5
-#endif
-  // -DMX_PRIO_P=.. etc. override one phase for an A/B
-#ifndef MX_PRIO_P
-#define MX_PRIO_P (MX_PRIO == 5 ? 3 : MX_PRIO == 4 ? 2 : (MX_PRIO == 2 || MX_PRIO == 3) ? 1 : 0)
-#endif
-#ifndef MX_PRIO_F
-#define MX_PRIO_F (MX_PRIO == 5 ? 2 : (MX_PRIO == 3 || MX_PRIO == 4) ? 1 : 0)
-#endif
-#ifndef MX_PRIO_R
-#define MX_PRIO_R ((MX_PRIO == 1 || MX_PRIO == 4 || MX_PRIO == 5) ? 1 : 0)
-#endif
-#ifndef MX_PRIO_R2
-#define MX_PRIO_R2 (MX_PRIO == 5 ? 0 : MX_PRIO_R)
-#endif
-#ifndef MX_PRIO_C
-#define MX_PRIO_C 0
-#endif
-  constexpr bool PRIO_ON = (MX_PRIO_P | MX_PRIO_F | MX_PRIO_R | MX_PRIO_R2 | MX_PRIO_C) != 0;
+  // The wave's issue priority by phase of the Montgomery product (s_setprio; the
+  // two waves of a SIMD are mostly in different phases). The levels fall along
+  // the product, so whenever the two waves are in different phases the one that
+  // is earlier in its product issues first and the other fills the slots it
+  // leaves: config 2 at 123.3 ms, the fastest of the orders tried
+  // (profiles/r06/prioab2..5).
+  constexpr int PRIO_PRODUCT = 3;  // product loop
+  constexpr int PRIO_FRAG = 2;     // fragment build
+  constexpr int PRIO_Q = 1;        // q products
+  constexpr int PRIO_QM = 0;       // q m products
+  constexpr int PRIO_CARRY = 0;    // carry passes
   MX_STAMP(0);
-  if constexpr (PRIO_ON) __builtin_amdgcn_s_setprio(MX_PRIO_P);
+  __builtin_amdgcn_s_setprio(PRIO_PRODUCT);
   if constexpr (MPCX_MX_TIMING != 2) mx_product<P, K, SQR, B2IN>(A, rg, rg, rows + S::TRASH_OFF + lane, p);
-  if constexpr (PRIO_ON) __builtin_amdgcn_s_setprio(MX_PRIO_F);
+  __builtin_amdgcn_s_setprio(PRIO_FRAG);
   MX_STAMP(1);
   if constexpr (MPCX_MX_TIMING == 1) return;
   wave_lds_fence();
@@ -325,11 +282,11 @@ __device__ __forceinline__ void montmul_mx(uint32_t (&A)[S::K], uint32_t* rows, 
   // ---- the row <- T's high digits + m (block layout)
 #pragma unroll
   for (int k = 0; k < K; ++k) rg[p * K + k] = A[k] + md[p * K + k];
-  if constexpr (PRIO_ON && MX_PRIO_R != MX_PRIO_F) __builtin_amdgcn_s_setprio(MX_PRIO_R);
+  __builtin_amdgcn_s_setprio(PRIO_Q);
   static_for<0, S::HALVES>([&](auto sc) {
     constexpr int s = decltype(sc)::value;
     uint32_t* rn = rows + (16 * s + n) * ROW;
-    if constexpr (PRIO_ON && MX_PRIO_R2 != MX_PRIO_R && s > 0) __builtin_amdgcn_s_setprio(MX_PRIO_R);
+    if constexpr (s > 0) __builtin_amdgcn_s_setprio(PRIO_Q);  // the first half left it at PRIO_QM
     // ---- q column sums (o = j + 4 kb; chunks of output blocks bound the live
     // accumulators), balanced radix-2^28 digits with one carry step, as bytes;
     // every 4 blocks transposed in registers into one B fragment of phase 2
@@ -338,17 +295,9 @@ __device__ __forceinline__ void montmul_mx(uint32_t (&A)[S::K], uint32_t* rows, 
       int xprev = 0;
       uint32_t X[4] = {0u, 0u, 0u, 0u};
       auto norm = [&](const mx_v4i& cs, int o) __attribute__((always_inline)) -> uint32_t {
-        int lo, hi;
-        if constexpr (MX_SPLIT_MAD) {
-          const int64_t v = mx_sum64(cs, 1 << 27);
-          lo = ((int)(uint32_t)v & (int)M28) - (1 << 27);
-          hi = mx_hi28(v);
-        } else {
-          int lo_sum, hi_sum;
-          mx_split(cs, 1 << 27, lo_sum, hi_sum);
-          lo = (lo_sum & (int)M28) - (1 << 27);
-          hi = hi_sum + (lo_sum >> 28);
-        }
+        const int64_t v = mx_sum64(cs, 1 << 27);
+        const int lo = ((int)(uint32_t)v & (int)M28) - (1 << 27);
+        const int hi = mx_hi28(v);
         const int x = mx_from_prev_quarter(hi, lane);
         int e = lo + (h == 0 ? xprev : x);
         xprev = x;
@@ -377,7 +326,7 @@ __device__ __forceinline__ void montmul_mx(uint32_t (&A)[S::K], uint32_t* rows, 
       });
     }
     MX_STAMP(3);
-    if constexpr (PRIO_ON && MX_PRIO_R2 != MX_PRIO_R) __builtin_amdgcn_s_setprio(MX_PRIO_R2);
+    __builtin_amdgcn_s_setprio(PRIO_QM);
     // ---- q m column sums for blocks O2LO.. : the lane whose 4 positions are the
     // low half's top (N7 - 4 .. N7 - 1) gives the carry out of the low half, the
     // lanes at positions N7 + 4d the digits d of U + m, adding T's high digit + m
@@ -390,19 +339,10 @@ __device__ __forceinline__ void montmul_mx(uint32_t (&A)[S::K], uint32_t* rows, 
         const int d = (pos - S::N7) >> 2;  // U's digit (< 0: the low half)
         const int dc = d < 0 ? 0 : d;
         const int add = carry_lane ? ttop[s] + (1 << 27) : (int)rn[dc];
-        int hi, dig, top;  // dig: the sum's bits 0..27; top: the sum mod 2^32
-        if constexpr (MX_SPLIT_MAD) {
-          const int64_t v = mx_sum64(cs, add);
-          hi = mx_hi28(v);  // on the carry lane: round(low half / R)
-          top = (int)(uint32_t)v;
-          dig = top & (int)M28;
-        } else {
-          int lo_sum, hi_sum;
-          mx_split(cs, add, lo_sum, hi_sum);
-          hi = hi_sum + (lo_sum >> 28);
-          top = (int)((uint32_t)lo_sum + ((uint32_t)hi_sum << 28));
-          dig = lo_sum & (int)M28;
-        }
+        const int64_t v = mx_sum64(cs, add);
+        const int hi = mx_hi28(v);        // on the carry lane: round(low half / R)
+        const int top = (int)(uint32_t)v;  // the sum mod 2^32
+        const int dig = top & (int)M28;    // the sum's bits 0..27
         const int x = mx_from_prev_quarter(hi, lane);
         const int cin = h == 0 ? xprev : x;
         xprev = x;
@@ -421,27 +361,20 @@ __device__ __forceinline__ void montmul_mx(uint32_t (&A)[S::K], uint32_t* rows, 
       });
     }
   });
-  if constexpr (PRIO_ON) __builtin_amdgcn_s_setprio(MX_PRIO_C);
+  __builtin_amdgcn_s_setprio(PRIO_CARRY);
   MX_STAMP(4);
   wave_lds_fence();
   // ---- back to the block layout; signed carry passes until every digit is >= 0
 #pragma unroll
   for (int k = 0; k < K; ++k) A[k] = rg[p * K + k];
   MX_STAMP(5);
-  // MX_CARRY_SKIP: the emitted digits lie in (-2^16, 2^28 + 2^16) (one carry step
-  // of |carry| < 2^16); the next product takes any non-negative digits of that
-  // size (its 64-bit accumulators have the room), so the passes run only when
-  // some digit of the wave is negative (~1 wave in 4)
-#ifndef MX_CARRY_SKIP
-#define MX_CARRY_SKIP 1
-#endif
-  bool need = true;
-  if constexpr (MX_CARRY_SKIP) {
-    uint32_t sg = 0;
+  // the emitted digits lie in (-2^16, 2^28 + 2^16) (one carry step of |carry| <
+  // 2^16); the next product takes any non-negative digits of that size, so the
+  // passes run only when some digit of the wave is negative (~1 wave in 4)
+  uint32_t sg = 0;
 #pragma unroll
-    for (int k = 0; k < K; ++k) sg |= A[k];
-    need = __any((int)sg < 0);
-  }
+  for (int k = 0; k < K; ++k) sg |= A[k];
+  const bool need = __any((int)sg < 0);
   for (int it = 0; need && it < L + 2; ++it) {
     const int top = (int)A[K - 1];
     const int ctop = (p == P - 1) ? 0 : (top >> DB);

@@ -55,7 +55,7 @@ __global__ __launch_bounds__(64 * MX_WG) __attribute__((amdgpu_waves_per_eu(MXB_
   for (uint32_t s = 0; s < S; ++s) {
     lds_store_sqr<MX_K>(rows + g * MxG2::ROW, p, A);
     wave_lds_fence();
-    montmul_mx<MxG2, true, (bool)MPCX_SQR_B2>(A, rows, md, c, lane PROF_ARG);
+    montmul_mx<MxG2, true, true>(A, rows, md, c, lane PROF_ARG);
     wave_lds_fence();
   }
 #ifdef MX_PROF
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
   for (uint32_t s = 0; s < S; ++s) {
     lds_store_sqr<MX_K>(bl, p, A);
     wave_lds_fence();
-    montmul<MX_P, MX_K, true, (bool)MPCX_SQR_B2>(A, bl, Nd, n0inv, 0, p);
+    montmul<MX_P, MX_K, true, true>(A, bl, Nd, n0inv, 0, p);
     wave_lds_fence();
   }
   if (op < count) {
