@@ -418,8 +418,6 @@ int mpcx_sync(void* stream);
  *                the GPU's SIMD time in the launch-time model (latency +
  *                weight x share). 150 / 300 measured neutral to slower (same
  *                A/B). Environment: MPCX_GEOM_TPUT.
- *   "prime_coop" 1 (default): cooperative per-candidate prime kernels; 0:
- *                thread per candidate.
  *   "lanes"      1..8 (default 6, or MPCX_LANES): execution lanes (streams
  *                with their own workspaces) per device used from now on.
  *   "device_split_min" operands (default 4096): smallest per-device slice
@@ -438,7 +436,7 @@ int mpcx_sync(void* stream);
  *                with an event pair for mpcx_kernel_stats.
  * Environment, read at mpcx_init / mpcx_init_devices: MPCX_LANES (1..8,
  * default 6: execution lanes per device), MPCX_GEOM_POLICY, MPCX_NARROW_ROUNDS,
- * MPCX_PRIME_COOP, MPCX_FB_WINDOW, MPCX_MX, MPCX_MX_STEP, MPCX_GEOM_TPUT. */
+ * MPCX_FB_WINDOW, MPCX_MX, MPCX_MX_STEP, MPCX_GEOM_TPUT. */
 int mpcx_set_option(const char* key, int value);
 /* Current value of "mx", "mx_min", "mx_seg_min", "mx_step", "geom_tput",
  * "geom_policy", "sched_width", "fixed_window", "fb_split" or "lanes"

@@ -186,7 +186,7 @@ std::vector<uint8_t> ProbablyPrimeBatch(const std::vector<Nat>& n, int reps, Saf
     if (!div) live.push_back(i);
   }
   // Miller-Rabin: base 2 first; the other bases only for its survivors
-  std::vector<size_t> small, large;  // GPU thread-per-candidate class (< 2^1024) / wider
+  std::vector<size_t> small, large;  // the GPU's k_mrc / k_lucasc class (< 2^1024) / wider
   for (size_t i : live) (n[i].bit_len() <= 1024 ? small : large).push_back(i);
   uint64_t mr = 0, lt = 0;
   if (!small.empty()) {

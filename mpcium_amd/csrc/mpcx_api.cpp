@@ -49,11 +49,8 @@
 static_assert(MPCX_NUM_GEOMS == 7, "update MPCX_FOR_EACH_GEOM and build.py GEOMS");
 extern "C" {
 MPCX_FOR_EACH_GEOM(MPCX_GEOM_DECL)
-hipError_t mpcx_launch_prime2(const mpcx::Prime2Args* a, uint32_t blocks, hipStream_t st);
-hipError_t mpcx_launch_lucas(const mpcx::LucasArgs* a, uint32_t blocks, hipStream_t st);
 hipError_t mpcx_launch_drbg(const mpcx::DrbgArgs* a, hipStream_t st);
-hipError_t mpcx_launch_mr(const mpcx::MrArgs* a, uint32_t blocks, hipStream_t st);
-hipError_t mpcx_launch_prime2c(const mpcx::Prime2Args* a, hipStream_t st);
+hipError_t mpcx_launch_prime2c(mpcx::Prime2Args a, hipStream_t st);
 hipError_t mpcx_launch_mrc(const mpcx::MrArgs* a, hipStream_t st);
 hipError_t mpcx_launch_lucasc(const mpcx::LucasArgs* a, hipStream_t st);
 hipError_t mpcx_launch_lucasc_wide(const mpcx::LucasArgs* a, hipStream_t st);
@@ -122,7 +119,6 @@ int g_fb_window = MPCX_FB_WINDOW_BITS;  // mpcx_set_option("fb_window", w): fixe
 #endif
 int g_fb_split = MPCX_FB_SPLIT_DEFAULT;  // mpcx_set_option("fb_split", s): comb waves per workgroup (0: by size)
 uint32_t g_split_min = 4096;             // mpcx_set_option("device_split_min", n): operands per device slice
-bool g_prime_coop = true;                // mpcx_set_option("prime_coop", 0): thread-per-candidate prime kernels
 bool g_dup_device = false;               // mpcx_set_option("duplicate_device", 1): test hook, see below
 #ifndef MPCX_MX_DEFAULT
 #define MPCX_MX_DEFAULT 1
@@ -155,7 +151,7 @@ struct Lane {
   Staging stage[4];  // bases, exps, out, misc
   // safe-prime step: survivors' p words, survivors' indices, trial-division
   // tables + counters, Fermat passes' p words, their indices, ride-along q +
-  // verdicts, per-item constants of the cooperative kernels (R mod n, meta)
+  // verdicts, k_prime2c's per-item constants (R mod n, meta)
   Staging sieve[8];
   // kernel timing (mpcx_kernel_stats): event pairs around this lane's
   // launches, resolved at the lane's next host wait; guarded by mu like the rest
@@ -1577,9 +1573,6 @@ int mpcx_set_option(const char* key, int value) {
     // main (throughput) geometry of the geometry's class
     if (value < 0 || value >= MPCX_NUM_GEOMS) return fail(MPCX_EINVAL, "main_geom %d out of range", value);
     g_main_geom[MPCX_GEOM_CLASS(value)] = value;
-  } else if (std::strcmp(key, "prime_coop") == 0) {
-    // 1: cooperative base-2 / Miller-Rabin kernels (k_prime2c, k_mrc); 0: thread per candidate
-    g_prime_coop = value != 0;
   } else if (std::strcmp(key, "duplicate_device") == 0) {
     // test hook: mpcx_init(ordinal) binds an already bound ordinal again as another logical device
     g_dup_device = value != 0;
@@ -1611,8 +1604,6 @@ int mpcx_device_count(int* out_count) {
 static void read_env_options() {
   const char* nr = std::getenv("MPCX_NARROW_ROUNDS");  // percent of a main round
   if (nr) g_narrow_rounds = std::max(0, std::min(100, std::atoi(nr))) / 100.0;
-  const char* pc = std::getenv("MPCX_PRIME_COOP");
-  if (pc) g_prime_coop = pc[0] != '0';
   const char* gp = std::getenv("MPCX_GEOM_POLICY");
   if (gp) g_geom_policy = std::max(0, std::min(2, std::atoi(gp)));
   const char* ln = std::getenv("MPCX_LANES");
@@ -2356,8 +2347,8 @@ int mpcx_fermat2_batch(uint32_t count, const uint32_t* p, uint32_t p_words, uint
     if ((rc = lane_stream(l))) return rc;
     const size_t pb = (size_t)n * p_words * 4;
     if ((rc = ensure_buffer(l.stage[0], pb)) || (rc = ensure_buffer(l.stage[3], n)) ||
-        (g_prime_coop && ((rc = ensure_buffer(l.stage[1], (size_t)n * MPCX_PRIME_L * 4)) ||
-                          (rc = ensure_buffer(l.stage[2], (size_t)n * 8)))))
+        (rc = ensure_buffer(l.stage[1], (size_t)n * MPCX_PRIME_L * 4)) ||
+        (rc = ensure_buffer(l.stage[2], (size_t)n * 8)))
       return rc;
     if ((rc = h2d(l, l.stage[0].ptr, p + (size_t)first * p_words, pb))) return rc;
     mpcx::Prime2Args a{};
@@ -2365,18 +2356,10 @@ int mpcx_fermat2_batch(uint32_t count, const uint32_t* p, uint32_t p_words, uint
     a.count_f = n;
     a.ok_f = (uint8_t*)l.stage[3].ptr;
     a.n_words = p_words;
-    hipError_t e;
-    if (g_prime_coop) {
-      a.f_blocks = (n + 64 / MPCX_PRIME_P - 1) / (64 / MPCX_PRIME_P);
-      a.fp_blocks = (n + 63) / 64;
-      a.r1 = (uint32_t*)l.stage[1].ptr;
-      a.meta = (uint32_t*)l.stage[2].ptr;
-      e = mpcx_launch_prime2c(&a, l.st);
-    } else {
-      a.f_blocks = (n + 63) / 64;
-      e = mpcx_launch_prime2(&a, a.f_blocks, l.st);
-    }
-    if (e != hipSuccess) return hip_fail(e, "launch k_prime2");
+    a.r1 = (uint32_t*)l.stage[1].ptr;
+    a.meta = (uint32_t*)l.stage[2].ptr;
+    const hipError_t e = mpcx_launch_prime2c(a, l.st);
+    if (e != hipSuccess) return hip_fail(e, "launch k_prime2c");
     return d2h_sync(ok + first, l.stage[3].ptr, n, l);
   });
 }
@@ -2399,8 +2382,7 @@ int mpcx_mr_batch(uint32_t count, const uint32_t* n, uint32_t n_words, const uin
     if ((rc = lane_stream(l))) return rc;
     const size_t nb = (size_t)cnt * n_words * 4;
     if ((rc = ensure_buffer(l.stage[0], nb)) || (rc = ensure_buffer(l.stage[1], nb)) ||
-        (rc = ensure_buffer(l.stage[3], cnt)) ||
-        (g_prime_coop && (rc = ensure_buffer(l.stage[2], (size_t)cnt * (MPCX_MR_L + 2) * 4))))
+        (rc = ensure_buffer(l.stage[3], cnt)) || (rc = ensure_buffer(l.stage[2], (size_t)cnt * (MPCX_MR_L + 2) * 4)))
       return rc;
     if ((rc = h2d(l, l.stage[0].ptr, n + (size_t)first * n_words, nb)) ||
         (rc = h2d(l, l.stage[1].ptr, bases + (size_t)first * n_words, nb)))
@@ -2411,15 +2393,10 @@ int mpcx_mr_batch(uint32_t count, const uint32_t* n, uint32_t n_words, const uin
     a.ok = (uint8_t*)l.stage[3].ptr;
     a.count = cnt;
     a.n_words = n_words;
-    hipError_t e;
-    if (g_prime_coop) {
-      a.r1 = (uint32_t*)l.stage[2].ptr;
-      a.meta = a.r1 + (size_t)cnt * MPCX_MR_L;
-      e = mpcx_launch_mrc(&a, l.st);
-    } else {
-      e = mpcx_launch_mr(&a, (cnt + 63) / 64, l.st);
-    }
-    if (e != hipSuccess) return hip_fail(e, "launch k_mr");
+    a.r1 = (uint32_t*)l.stage[2].ptr;
+    a.meta = a.r1 + (size_t)cnt * MPCX_MR_L;
+    const hipError_t e = mpcx_launch_mrc(&a, l.st);
+    if (e != hipSuccess) return hip_fail(e, "launch k_mrc");
     return d2h_sync(ok + first, l.stage[3].ptr, cnt, l);
   });
 }
@@ -2437,7 +2414,7 @@ int mpcx_lucas_batch(uint32_t count, const uint32_t* n, uint32_t n_words, const 
     if (P[i] < 3 || P[i] >= (1u << 14)) return fail(MPCX_EINVAL, "Lucas parameter P[%u] = %u outside [3, 2^14)", i, P[i]);
     maxbits = std::max(maxbits, bits);
   }
-  // candidates above 1024 bits: the wide cooperative geometry (16 x 5 digits)
+  // candidates above 1024 bits: the wide geometry (16 x 5 digits)
   const bool wide = maxbits > 1024;
   const uint32_t cl = wide ? (uint32_t)MPCX_LUCASW_L : (uint32_t)MPCX_MR_L;
   return run_sliced(count, g_split_min, [&](int di, uint32_t first, uint32_t cnt) {
@@ -2448,8 +2425,7 @@ int mpcx_lucas_batch(uint32_t count, const uint32_t* n, uint32_t n_words, const 
     if ((rc = lane_stream(l))) return rc;
     const size_t nb = (size_t)cnt * n_words * 4;
     if ((rc = ensure_buffer(l.stage[0], nb)) || (rc = ensure_buffer(l.stage[1], (size_t)cnt * 4)) ||
-        (rc = ensure_buffer(l.stage[3], cnt)) ||
-        ((g_prime_coop || wide) && (rc = ensure_buffer(l.stage[2], (size_t)cnt * (4 * cl + 2) * 4))))
+        (rc = ensure_buffer(l.stage[3], cnt)) || (rc = ensure_buffer(l.stage[2], (size_t)cnt * (4 * cl + 2) * 4)))
       return rc;
     if ((rc = h2d(l, l.stage[0].ptr, n + (size_t)first * n_words, nb)) ||
         (rc = h2d(l, l.stage[1].ptr, P + first, (size_t)cnt * 4)))
@@ -2460,15 +2436,10 @@ int mpcx_lucas_batch(uint32_t count, const uint32_t* n, uint32_t n_words, const 
     a.ok = (uint8_t*)l.stage[3].ptr;
     a.count = cnt;
     a.n_words = n_words;
-    hipError_t e;
-    if (g_prime_coop || wide) {
-      a.consts = (uint32_t*)l.stage[2].ptr;
-      a.meta = a.consts + (size_t)cnt * 4 * cl;
-      e = wide ? mpcx_launch_lucasc_wide(&a, l.st) : mpcx_launch_lucasc(&a, l.st);
-    } else {
-      e = mpcx_launch_lucas(&a, (cnt + 63) / 64, l.st);
-    }
-    if (e != hipSuccess) return hip_fail(e, "launch k_lucas");
+    a.consts = (uint32_t*)l.stage[2].ptr;
+    a.meta = a.consts + (size_t)cnt * 4 * cl;
+    const hipError_t e = wide ? mpcx_launch_lucasc_wide(&a, l.st) : mpcx_launch_lucasc(&a, l.st);
+    if (e != hipSuccess) return hip_fail(e, "launch k_lucasc");
     return d2h_sync(ok + first, l.stage[3].ptr, cnt, l);
   });
 }
@@ -2940,8 +2911,7 @@ int safeprime_step_on(int di, uint64_t seed, const uint8_t* raw, uint64_t stream
       (rc = ensure_buffer(sv[3], (size_t)std::max<uint32_t>(max_pass, 1) * W * 4)) ||
       (rc = ensure_buffer(sv[4], (size_t)std::max<uint32_t>(max_pass, 1) * 4)) ||
       (rc = ensure_buffer(sv[5], (size_t)n_sprp * (W * 4 + 1) + 64)) || (all_ok && (rc = ensure_buffer(sg[3], cap))) ||
-      (g_prime_coop && ((rc = ensure_buffer(sv[6], (cap + n_sprp) * MPCX_PRIME_L * 4)) ||
-                        (rc = ensure_buffer(sv[7], (cap + n_sprp) * 8)))))
+      (rc = ensure_buffer(sv[6], (cap + n_sprp) * MPCX_PRIME_L * 4)) || (rc = ensure_buffer(sv[7], (cap + n_sprp) * 8)))
     return rc;
   std::vector<uint32_t> misc(misc_words, 0);
   std::copy(tt.prod.begin(), tt.prod.end(), misc.begin() + off_prod);
@@ -2986,7 +2956,6 @@ int safeprime_step_on(int di, uint64_t seed, const uint8_t* raw, uint64_t stream
   pa.nf = (const uint32_t*)sv[0].ptr;
   pa.count_f = count;
   pa.count_dev = dm;
-  pa.f_blocks = (count + 63) / 64;
   pa.ok_f = all_ok ? (uint8_t*)sg[3].ptr : nullptr;
   pa.sieve_idx = (const uint32_t*)sv[1].ptr;
   pa.pass_count = dm + 1;
@@ -2996,31 +2965,21 @@ int safeprime_step_on(int di, uint64_t seed, const uint8_t* raw, uint64_t stream
   pa.count_s = n_sprp;
   pa.ok_s = d_sok;
   pa.n_words = W;
-  if (g_prime_coop) {
-    pa.f_blocks = (count + 64 / MPCX_PRIME_P - 1) / (64 / MPCX_PRIME_P);
-    pa.fp_blocks = (count + 63) / 64;
-    pa.r1 = (uint32_t*)sv[6].ptr;
-    pa.meta = (uint32_t*)sv[7].ptr;
-    if (count || n_sprp) {
-      const int ks = kstat_begin(l);
-      e = mpcx_launch_prime2c(&pa, l.st);
-      if (e != hipSuccess) return hip_fail(e, "launch k_prime2c");
-      kstat_end(l, ks, g_devs[di], di, "prime2c", -1, 0, 0.0);  // work credited below from the survivor count
-    }
-  } else {
-    const uint32_t blocks = pa.f_blocks + (n_sprp + 63) / 64;
-    if (blocks) {
-      e = mpcx_launch_prime2(&pa, blocks, l.st);
-      if (e != hipSuccess) return hip_fail(e, "launch k_prime2");
-    }
+  pa.r1 = (uint32_t*)sv[6].ptr;
+  pa.meta = (uint32_t*)sv[7].ptr;
+  if (count || n_sprp) {
+    const int ks = kstat_begin(l);
+    e = mpcx_launch_prime2c(pa, l.st);
+    if (e != hipSuccess) return hip_fail(e, "launch k_prime2c");
+    kstat_end(l, ks, g_devs[di], di, "prime2c", -1, 0, 0.0);  // work credited below from the survivor count
   }
   uint32_t cnt2[2] = {0, 0};
   if ((rc = d2h_sync(cnt2, dm, 8, l))) return rc;
   const uint32_t ns = cnt2[0], np = cnt2[1];
   if (ns > count || np > ns) return fail(MPCX_EHIP, "safe-prime step counters %u/%u out of range (%u)", ns, np, count);
-  if (g_prime_coop)  // Go-equivalent work: 2^(p-1) mod p per survivor, 2^d mod q per ride-along q
-    kstat_credit("prime2c", -1, (uint64_t)ns + n_sprp, (double)ns * go_macs(q_bits + 1, q_bits + 1) +
-                                                           (double)n_sprp * go_macs(q_bits, q_bits));
+  // Go-equivalent work: 2^(p-1) mod p per survivor, 2^d mod q per ride-along q
+  kstat_credit("prime2c", -1, (uint64_t)ns + n_sprp,
+               (double)ns * go_macs(q_bits + 1, q_bits + 1) + (double)n_sprp * go_macs(q_bits, q_bits));
   if (np > max_pass) return fail(MPCX_ENOMEM, "%u Fermat passes > max_pass %u", np, max_pass);
   std::vector<uint32_t> pidx(np), pp((size_t)np * W);
   if (np && ((rc = d2h(l, pidx.data(), sv[4].ptr, (size_t)np * 4)) || (rc = d2h(l, pp.data(), sv[3].ptr, pp.size() * 4))))

@@ -54,17 +54,11 @@
 #ifndef MPCX_BLOCK_FENCE
 #define MPCX_BLOCK_FENCE 0  // 1: scheduling fence between montmul's P blocks (the prime kernels' TU sets it)
 #endif
-#ifndef MPCX_WAVES_PER_EU_FERMAT
-#define MPCX_WAVES_PER_EU_FERMAT 1
-#endif
 #ifndef MPCX_WAVES_PER_EU_PRIME2C
 #define MPCX_WAVES_PER_EU_PRIME2C 3
 #endif
 #ifndef MPCX_WAVES_PER_EU_MRC
 #define MPCX_WAVES_PER_EU_MRC 3
-#endif
-#ifndef MPCX_WAVES_PER_EU_MR
-#define MPCX_WAVES_PER_EU_MR 1
 #endif
 
 namespace mpcx {
@@ -847,10 +841,11 @@ __global__ __launch_bounds__(64 * MPCX_FB_MAX_SPLIT) __attribute__((amdgpu_waves
   fixedbase_wave<P, K, G>(segs[s], b - __builtin_amdgcn_readfirstlane(first[s]));
 }
 
-// ------------------------------------------- per-candidate-modulus helpers
-// Thread-per-operand kernels (P = 1, K digits per lane) whose modulus differs
-// per lane: safe-prime candidates. Every Montgomery constant is derived on the
-// device from the candidate itself.
+// ------------------------------------------------- primality-test kernels
+// The modulus is the candidate itself, so every Montgomery constant is derived
+// on the device. Serial digit helpers first (all K digits of a value in one
+// thread's registers): the thread-per-item prep kernels use them to work out
+// each candidate's constants once.
 template <int K>
 __device__ __forceinline__ bool ge_digits(const uint32_t (&x)[K], const uint32_t (&y)[K]) {
   // branch-free lexicographic compare from the top digit
@@ -882,18 +877,6 @@ __device__ __forceinline__ void norm_serial(uint32_t (&x)[K]) {
     c = t >> DB;
   }
 }
-template <int K>
-__device__ __forceinline__ void canon_serial(uint32_t (&x)[K], const uint32_t (&n)[K]) {
-  norm_serial<K>(x);
-  for (int it = 0; it < 8 && ge_digits<K>(x, n); ++it) sub_digits<K>(x, n);
-}
-template <int K>
-__device__ __forceinline__ bool eq_digits(const uint32_t (&x)[K], const uint32_t (&y)[K]) {
-  bool e = true;
-#pragma unroll
-  for (int k = 0; k < K; ++k) e &= x[k] == y[k];
-  return e;
-}
 // x = (x + y) mod-lazy: digit sum, normalised (no reduction)
 template <int K>
 __device__ __forceinline__ void add_digits(uint32_t (&x)[K], const uint32_t (&y)[K]) {
@@ -901,17 +884,15 @@ __device__ __forceinline__ void add_digits(uint32_t (&x)[K], const uint32_t (&y)
   for (int k = 0; k < K; ++k) x[k] += y[k];
   norm_serial<K>(x);
 }
-// candidate words -> radix-2^28 digits (inactive lanes: the odd dummy 1)
+// candidate words -> radix-2^28 digits
 template <int K>
-__device__ __forceinline__ void load_candidate(const uint32_t* w, uint32_t words, bool active, uint32_t (&Nd)[K]) {
+__device__ __forceinline__ void load_candidate(const uint32_t* w, uint32_t words, uint32_t (&Nd)[K]) {
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     const uint32_t bit = (uint32_t)k * DB, wi = bit >> 5, sh = bit & 31u;
-    uint64_t v = 0;
-    if (active) v = ((uint64_t)((wi + 1) < words ? w[wi + 1] : 0u) << 32) | (wi < words ? w[wi] : 0u);
+    const uint64_t v = ((uint64_t)((wi + 1) < words ? w[wi + 1] : 0u) << 32) | (wi < words ? w[wi] : 0u);
     Nd[k] = (uint32_t)(v >> sh) & M28;
   }
-  if (!active) Nd[0] = 1;
 }
 // -n^-1 mod 2^28 (Newton on 32 bits)
 __device__ __forceinline__ uint32_t neg_inv28(uint32_t n0) {
@@ -951,381 +932,18 @@ __device__ __forceinline__ void r_mod(const uint32_t (&Nd)[K], int nbits, uint32
 // bit j of the candidate (from its words in memory: no dynamic register index)
 __device__ __forceinline__ uint32_t word_bit(const uint32_t* w, int j) { return (w[j >> 5] >> (j & 31)) & 1u; }
 
-// -------------------------------------------- base-2 tests (k_prime2)
-// Fermat items: ok = 2^(n-1) == 1 (mod n) -- tss-lib's Pocklington check on
-// p = 2q+1 (up:common/safe_prime.go isPocklingtonCriterionSatisfied).
-// Strong items: n - 1 = 2^s d, x = 2^d; ok iff x == 1, or x^(2^j) == n-1
-// for some j < s -- the base-2 Miller-Rabin round of q.ProbablyPrime
-// (go:src/math/big/prime.go, its forced last base), run first so the other
-// rounds only see its survivors. One wave-uniform mode per block.
-// Square-and-double: squarings are Montgomery squarings and the "multiply by
-// 2" a digit doubling without reduction (values < 4n, and R > 16n keeps every
-// almost-Montgomery output below 2n).
-template <int K, int WPE>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void k_prime2(const Prime2Args a) {
-  constexpr int L = K;
-  __shared__ uint32_t lds[65 * L + 2];
-  const int lane = threadIdx.x;
-  const bool strong = blockIdx.x >= a.f_blocks;
-  uint32_t op, cnt;
-  const uint32_t* src;
-  if (!strong) {
-    cnt = a.count_dev ? min(a.count_f, *a.count_dev) : a.count_f;
-    if (blockIdx.x * 64u >= cnt) return;  // whole wave beyond the sieve's survivors
-    op = blockIdx.x * 64u + lane;
-    src = a.nf;
-  } else {
-    cnt = a.count_s;
-    if ((blockIdx.x - a.f_blocks) * 64u >= cnt) return;
-    op = (blockIdx.x - a.f_blocks) * 64u + lane;
-    src = a.ns;
-  }
-  const bool active = op < cnt;
-  uint32_t* bl = lds + lane * L;
-  const uint32_t* nw = src + (size_t)(active ? op : 0) * a.n_words;
-  uint32_t Nd[K], A[K], R1[K];
-  load_candidate<K>(nw, a.n_words, active, Nd);
-  const uint32_t n0inv = neg_inv28(Nd[0]);
-  const int nbits = bitlen_digits<K>(Nd);
-  r_mod<K>(Nd, nbits, R1);
-  int s = 0;  // Fermat: e = n - 1; strong: e = (n - 1) >> s, s = v2(n - 1)
-  if (strong && active) {
-    s = 1;
-    while (s < nbits && !word_bit(nw, s)) ++s;
-  }
-  // the top bit of e is the top bit of n: start from Montgomery 2
-#pragma unroll
-  for (int k = 0; k < K; ++k) A[k] = R1[k] << 1;
-  norm_serial<K>(A);
-  const int m_src_addr = lane * 4;
-  for (int i = nbits - s - 2; i >= 0; --i) {
-    lds_store_digits<K>(bl, 0, A);
-    wave_lds_fence();
-    montmul<1, K, true>(A, bl, Nd, n0inv, m_src_addr, 0);
-    wave_lds_fence();
-    const int j = i + s;  // bit j of n - 1: bit j of n, except bit 0 (n odd)
-    if (j > 0 && active && word_bit(nw, j)) {
-#pragma unroll
-      for (int k = 0; k < K; ++k) A[k] <<= 1;
-      norm_serial<K>(A);
-    }
-  }
-  canon_serial<K>(A, Nd);
-  bool pass = eq_digits<K>(A, R1);  // 2^e == 1
-  if (strong) {
-    uint32_t NR1[K];  // Montgomery form of n - 1
-#pragma unroll
-    for (int k = 0; k < K; ++k) NR1[k] = Nd[k];
-    sub_digits<K>(NR1, R1);
-    pass = pass || eq_digits<K>(A, NR1);
-    for (int j = 1; j < s && !pass; ++j) {
-      lds_store_digits<K>(bl, 0, A);
-      wave_lds_fence();
-      montmul<1, K, true>(A, bl, Nd, n0inv, m_src_addr, 0);
-      wave_lds_fence();
-      canon_serial<K>(A, Nd);
-      if (eq_digits<K>(A, R1)) break;  // nontrivial square root of 1: composite
-      pass = eq_digits<K>(A, NR1);
-    }
-  }
-  if (!active) return;
-  if (strong) {
-    a.ok_s[op] = pass ? 1 : 0;
-    return;
-  }
-  if (a.ok_f) a.ok_f[op] = pass ? 1 : 0;
-  if (pass && a.pass_count) {
-    const uint32_t slot = atomicAdd(a.pass_count, 1u);
-    a.pass_idx[slot] = a.sieve_idx ? a.sieve_idx[op] : op;
-    for (uint32_t w = 0; w < a.n_words; ++w) a.pass_n[(size_t)slot * a.n_words + w] = nw[w];
-  }
-}
-
-// -------------------------------------------- strong Lucas test (k_lucas)
-// Go math/big probablyPrimeLucas (go:src/math/big/prime.go), the last step of
-// ProbablyPrime: with P from Baillie-OEIS method C (the smallest P >= 3 with
-// Jacobi(P^2 - 4, n) = -1, found by the caller; Q = 1), n + 1 = 2^r s (s odd):
-// n passes iff V_s == +-2 and U_s == 0 (checked as P V_s == 2 V_{s+1},
-// Crandall-Pomerance 3.13), or V_{2^t s} == 0 for some 0 <= t < r - 1.
-// V is built by the binary ladder V_2k = V_k^2 - 2, V_2k+1 = V_k V_k+1 - P in
-// the Montgomery domain: each step is one product and one squaring for every
-// lane (the bit only selects where the two results go, so the wave never
-// diverges); the subtractions are additions of 2n - c (values stay < 4n).
-template <int K, int WPE>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void k_lucas(const LucasArgs a) {
-  constexpr int L = K;
-  __shared__ uint32_t lds[65 * L + 2];
-  const int lane = threadIdx.x;
-  const uint32_t op = blockIdx.x * 64u + lane;
-  if (blockIdx.x * 64u >= a.count) return;
-  const bool active = op < a.count;
-  uint32_t* bl = lds + lane * L;
-  const int m_src_addr = lane * 4;
-  const uint32_t* nw = a.n + (size_t)(active ? op : 0) * a.n_words;
-  uint32_t Nd[K], R1[K];
-  load_candidate<K>(nw, a.n_words, active, Nd);
-  const uint32_t n0inv = neg_inv28(Nd[0]);
-  const int nbits = bitlen_digits<K>(Nd);
-  r_mod<K>(Nd, nbits, R1);
-  const uint32_t P = active ? a.P[op] : 3u;
-  // PR = P R mod n (Horner over P's bits), TwoR = 2 R mod n
-  uint32_t PR[K], TwoR[K], N2[K], CP[K], C2[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) PR[k] = 0;
-  for (int b = 13; b >= 0; --b) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) PR[k] <<= 1;
-    norm_serial<K>(PR);
-    if (ge_digits<K>(PR, Nd)) sub_digits<K>(PR, Nd);
-    if ((P >> b) & 1u) {
-      add_digits<K>(PR, R1);
-      if (ge_digits<K>(PR, Nd)) sub_digits<K>(PR, Nd);
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    TwoR[k] = R1[k] << 1;
-    N2[k] = Nd[k] << 1;
-  }
-  norm_serial<K>(TwoR);
-  if (ge_digits<K>(TwoR, Nd)) sub_digits<K>(TwoR, Nd);
-  norm_serial<K>(N2);
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    CP[k] = N2[k];
-    C2[k] = N2[k];
-  }
-  sub_digits<K>(CP, PR);    // 2n - P R: adding it subtracts P
-  sub_digits<K>(C2, TwoR);  // 2n - 2 R
-  // n + 1 = 2^r s: r = trailing ones of n; bit j of n + 1 is 0 below r, 1 at
-  // r, and bit j of n above
-  int r = 0;
-  if (active)
-    while (r < nbits && word_bit(nw, r)) ++r;
-  const int sbits = (r == nbits) ? 1 : nbits - r;
-  uint32_t vk[K], vk1[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    vk[k] = TwoR[k];  // V_0 = 2
-    vk1[k] = PR[k];   // V_1 = P
-  }
-  for (int i = sbits - 1; i >= 0; --i) {
-    const int j = i + r;
-    const bool bit = (j == r) || (active && word_bit(nw, j));
-    // X = V_k V_k+1 - P; Y = (bit ? V_k+1 : V_k)^2 - 2
-    uint32_t X[K], Y[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      X[k] = vk[k];
-      Y[k] = bit ? vk1[k] : vk[k];
-    }
-    lds_store_digits<K>(bl, 0, vk1);
-    wave_lds_fence();
-    montmul<1, K, false>(X, bl, Nd, n0inv, m_src_addr, 0);
-    wave_lds_fence();
-    add_digits<K>(X, CP);
-    lds_store_digits<K>(bl, 0, Y);
-    wave_lds_fence();
-    montmul<1, K, true>(Y, bl, Nd, n0inv, m_src_addr, 0);
-    wave_lds_fence();
-    add_digits<K>(Y, C2);
-    // bit: k' = 2k+1 -> (V_2k+1, V_2k+2) = (X, Y); else k' = 2k -> (V_2k, V_2k+1) = (Y, X)
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      vk[k] = bit ? X[k] : Y[k];
-      vk1[k] = bit ? Y[k] : X[k];
-    }
-  }
-  uint32_t NTwoR[K];  // Montgomery form of n - 2
-#pragma unroll
-  for (int k = 0; k < K; ++k) NTwoR[k] = Nd[k];
-  sub_digits<K>(NTwoR, TwoR);
-  canon_serial<K>(vk, Nd);
-  bool pass = false;
-  if (eq_digits<K>(vk, TwoR) || eq_digits<K>(vk, NTwoR)) {
-    // U_s == 0  <=>  P V_s == 2 V_s+1 (mod n)
-    uint32_t U1[K], U2[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      U1[k] = vk[k];
-      U2[k] = vk1[k];
-    }
-    lds_store_digits<K>(bl, 0, PR);
-    wave_lds_fence();
-    montmul<1, K, false>(U1, bl, Nd, n0inv, m_src_addr, 0);  // P V_s R
-    wave_lds_fence();
-    canon_serial<K>(U1, Nd);
-    add_digits<K>(U2, vk1);  // 2 V_s+1 R (< 8n)
-    canon_serial<K>(U2, Nd);
-    pass = eq_digits<K>(U1, U2);
-  }
-  for (int t = 0; t < r - 1 && !pass; ++t) {
-    bool zero = true;
-#pragma unroll
-    for (int k = 0; k < K; ++k) zero &= vk[k] == 0u;
-    if (zero) {
-      pass = true;
-      break;
-    }
-    if (eq_digits<K>(vk, TwoR)) break;  // V = 2 is a fixed point of V^2 - 2: never 0
-    lds_store_digits<K>(bl, 0, vk);
-    wave_lds_fence();
-    montmul<1, K, true>(vk, bl, Nd, n0inv, m_src_addr, 0);
-    wave_lds_fence();
-    add_digits<K>(vk, C2);
-    canon_serial<K>(vk, Nd);
-  }
-  if (active) a.ok[op] = pass ? 1 : 0;
-}
-
-// ---------------------------------------------------------- Miller-Rabin
-// ok[i] = n_i is a strong probable prime to base a_i (one candidate per lane,
-// per-lane modulus): n - 1 = 2^s d, x = a^d; pass iff x == 1 or x^(2^j) == n-1
-// for some j < s. Serves q.ProbablyPrime(20) in the safe-prime search
-// (up:common/safe_prime.go). All Montgomery constants are derived on the
-// device: R mod n by doubling, R^2 mod n = Mont(2^(28K)) by square-and-double.
-template <int K, int WPE>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void k_mr(const MrArgs a) {
-  constexpr int L = K;
-  __shared__ uint32_t lds[2 * 65 * L + 2];
-  const int lane = threadIdx.x;
-  const uint32_t op = blockIdx.x * 64u + lane;
-  const bool active = op < a.count;
-  uint32_t* bt = lds + lane * L;             // row for the running value (squarings)
-  uint32_t* bm = lds + (65 + lane) * L;      // row for a*R (multiplies)
-  const int m_src_addr = lane * 4;
-  const uint32_t* nw = a.n + (size_t)(active ? op : 0) * a.n_words;
-  const uint32_t* aw = a.a + (size_t)(active ? op : 0) * a.n_words;
-  uint32_t Nd[K], A[K], X[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-    const uint32_t bit = (uint32_t)k * DB, w = bit >> 5, sh = bit & 31u;
-    uint64_t v = 0, u = 0;
-    if (active) {
-      v = ((uint64_t)((w + 1) < a.n_words ? nw[w + 1] : 0u) << 32) | (w < a.n_words ? nw[w] : 0u);
-      u = ((uint64_t)((w + 1) < a.n_words ? aw[w + 1] : 0u) << 32) | (w < a.n_words ? aw[w] : 0u);
-    }
-    Nd[k] = (uint32_t)(v >> sh) & M28;
-    X[k] = (uint32_t)(u >> sh) & M28;
-  }
-  if (!active) Nd[0] = 1;
-  uint32_t inv = Nd[0];
-  for (int i = 0; i < 5; ++i) inv *= 2u - Nd[0] * inv;
-  const uint32_t n0inv = (0u - inv) & M28;
-  int nbits = 1;
-#pragma unroll
-  for (int k = 0; k < K; ++k)
-    if (Nd[k] != 0u) nbits = k * DB + (32 - __builtin_clz(Nd[k]));
-  // R mod n
-#pragma unroll
-  for (int k = 0; k < K; ++k) A[k] = 0;
-  {
-    uint32_t c = 1;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      const int lo = k * DB;
-      uint32_t maskk = 0;
-      if (nbits >= lo + DB) maskk = M28;
-      else if (nbits > lo) maskk = (1u << (nbits - lo)) - 1u;
-      const uint32_t t = ((~Nd[k]) & maskk) + c;
-      c = t >> DB;
-      A[k] = t & maskk;
-    }
-  }
-  for (int i = nbits; i < DB * K; ++i) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) A[k] <<= 1;
-    norm_serial<K>(A);
-    if (ge_digits<K>(A, Nd)) sub_digits<K>(A, Nd);
-  }
-  uint32_t R1[K];  // R mod n, canonical: Montgomery form of 1
-#pragma unroll
-  for (int k = 0; k < K; ++k) R1[k] = A[k];
-  // R^2 mod n = Mont(2^(28K)): square-and-double over the bits of E = 28K
-  constexpr int E = DB * K;
-  constexpr int ETOP = 31 - __builtin_clz((unsigned)E);
-#pragma unroll
-  for (int k = 0; k < K; ++k) A[k] <<= 1;  // Mont(2) (top bit of E)
-  norm_serial<K>(A);
-  for (int i = ETOP - 1; i >= 0; --i) {
-    lds_store_digits<K>(bt, 0, A);
-    wave_lds_fence();
-    montmul<1, K, true>(A, bt, Nd, n0inv, m_src_addr, 0);
-    wave_lds_fence();
-    if ((E >> i) & 1) {
-#pragma unroll
-      for (int k = 0; k < K; ++k) A[k] <<= 1;
-    }
-    norm_serial<K>(A);
-  }
-  // a*R = mont(a, R^2)
-  lds_store_digits<K>(bt, 0, A);
-  wave_lds_fence();
-#pragma unroll
-  for (int k = 0; k < K; ++k) A[k] = X[k];
-  montmul<1, K, false>(A, bt, Nd, n0inv, m_src_addr, 0);
-  wave_lds_fence();
-  lds_store_digits<K>(bm, 0, A);
-  // n - 1 = 2^s d (n odd, n >= 5): s = number of trailing zero bits of n-1
-  int s = 1;
-  while (s < nbits && !((nw[s >> 5] >> (s & 31)) & 1u)) ++s;
-  if (!active) s = 1;
-  const int dbits = nbits - s;  // bit length of d
-  // x = a^d, left to right binary (d's top bit is set)
-  for (int i = dbits - 2; i >= 0; --i) {
-    wave_lds_fence();
-    lds_store_digits<K>(bt, 0, A);
-    wave_lds_fence();
-    montmul<1, K, true>(A, bt, Nd, n0inv, m_src_addr, 0);
-    const uint32_t bit = active ? (nw[(i + s) >> 5] >> ((i + s) & 31)) & 1u : 0u;
-    if (bit) {
-      wave_lds_fence();
-      montmul<1, K, false>(A, bm, Nd, n0inv, m_src_addr, 0);
-    }
-  }
-  // compare in the Montgomery domain: 1 -> R1, n-1 -> n - R1
-  uint32_t NR1[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) NR1[k] = Nd[k];
-  {
-    uint32_t br = 0;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      const uint32_t t = NR1[k] - R1[k] - br;
-      br = (t >> 31) & 1u;
-      NR1[k] = t & M28;
-    }
-  }
-  auto eq = [&](const uint32_t (&x)[K], const uint32_t (&y)[K]) __attribute__((always_inline)) {
-    bool e = true;
-#pragma unroll
-    for (int k = 0; k < K; ++k) e &= x[k] == y[k];
-    return e;
-  };
-  canon_serial<K>(A, Nd);
-  bool pass = eq(A, R1) || eq(A, NR1);
-  for (int j = 1; j < s && !pass; ++j) {
-    wave_lds_fence();
-    lds_store_digits<K>(bt, 0, A);
-    wave_lds_fence();
-    montmul<1, K, true>(A, bt, Nd, n0inv, m_src_addr, 0);
-    canon_serial<K>(A, Nd);
-    if (eq(A, R1)) break;  // nontrivial square root of 1: composite
-    pass = eq(A, NR1);
-  }
-  if (active) a.ok[op] = pass ? 1 : 0;
-}
-
-// ------------------------------------ cooperative per-candidate kernels
-// The thread-per-candidate kernels above hold K = 37 digits per lane and run
-// one wavefront per SIMD, where a lone wave issues v_mad_u64_u32 at ~45% of
-// the SIMD peak (profiles/r01): a Fermat launch is capped there, and a small
-// Miller-Rabin or Lucas batch is one thread's full serial latency. The
-// kernels below give each candidate P lanes (K digits each, the k_modexp
-// montmul with a per-group modulus and -n^-1): P = 2 x K = 19 for the base-2
-// throughput tests (32 candidates and 3 waves per SIMD), P = 16 x K = 3 for
-// general-base Miller-Rabin (4 tests per wave, 1/8 of the serial chain).
-// Per-item constants come from a thread-per-item prep kernel.
+// ------------------------------------------ P lanes per candidate
+// Each test runs as two launches. A thread-per-item prep kernel (k_pprep_*)
+// writes the candidate's constants with the serial helpers above; the test
+// kernel then gives each candidate P lanes of K digits each and runs the
+// k_modexp montmul with a per-group modulus and -n^-1: P = 2 x K = 19 for the
+// base-2 throughput tests (32 candidates per wave, 3 waves per SIMD),
+// P = 16 x K = 3 for general-base Miller-Rabin and strong Lucas (4 tests per
+// wave, 1/8 of one thread's serial chain; K = 5 for Lucas candidates above
+// 1024 bits). Round 1 held one candidate per lane (1 x 37); that ran one
+// wavefront per SIMD at ~45% of the v_mad_u64_u32 peak and made a small batch
+// wait for one thread's full serial chain, so P lanes per candidate won
+// (DESIGN.md 5.3).
 
 // R mod n (canonical, L digits), -n^-1 mod 2^28 and nbits | s << 16
 // (s = v2(n - 1)) of one odd n >= 5 for R = 2^(28 L): 28 L - nbits doublings,
@@ -1333,7 +951,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
 template <int L>
 __device__ __forceinline__ void pprep_item(const uint32_t* nw, uint32_t n_words, uint32_t* r1_out, uint32_t* meta_out) {
   uint32_t Nd[L], R1[L];
-  load_candidate<L>(nw, n_words, true, Nd);
+  load_candidate<L>(nw, n_words, Nd);
   const int nbits = bitlen_digits<L>(Nd);
   r_mod<L>(Nd, nbits, R1);
   int s = 1;
@@ -1434,11 +1052,19 @@ __device__ __forceinline__ void double_digits(uint32_t (&A)[K], bool on) {
   carry_pass32<P, K>(A);
 }
 
-// Base-2 tests of k_prime2, P lanes per candidate: Fermat items
-// (2^(n-1) == 1) in blocks [0, f_blocks), strong items (n - 1 = 2^s d:
-// 2^d == 1, or 2^(2^j d) == n - 1 for some j < s) after them. Square and
-// double as in k_prime2 (values < 4n, R > 16n); the exponent bits differ per
-// candidate, so the doubling is a per-lane shift by 0 or 1.
+// Base-2 tests of the safe-prime search, P lanes per candidate, one
+// wave-uniform mode per block.
+// Fermat items, blocks [0, f_blocks): ok = 2^(n-1) == 1 (mod n) -- tss-lib's
+// Pocklington check on p = 2q+1 (up:common/safe_prime.go
+// isPocklingtonCriterionSatisfied).
+// Strong items, the blocks after them: n - 1 = 2^s d, x = 2^d; ok iff x == 1,
+// or x^(2^j) == n - 1 for some j < s -- the base-2 Miller-Rabin round of
+// q.ProbablyPrime (go:src/math/big/prime.go, its forced last base), run first
+// so the other rounds only see its survivors.
+// Square-and-double: squarings are Montgomery squarings and the "multiply by
+// 2" a digit doubling without reduction (values < 4n, and R > 16n keeps every
+// almost-Montgomery output below 2n); the exponent bits differ per candidate,
+// so the doubling is a per-lane shift by 0 or 1.
 template <int P, int K, int WPE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void k_prime2c(const Prime2Args a) {
   constexpr int L = P * K, G = 64 / P;
@@ -1563,11 +1189,14 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
   }
 }
 
-// Miller-Rabin to arbitrary bases, P lanes per test: R^2 mod n by
-// square-and-double from Mont(2), a R = mont(a, R^2), a 16-entry table
-// T[v] = a^v R in the group's LDS rows, then x = a^d by Go's 4-bit fixed
-// window (4 squarings and one table product per window for every lane: the
-// wave never diverges) and the strong check. ok[i] as k_mr.
+// Miller-Rabin to arbitrary bases, P lanes per test: ok[i] = n_i is a strong
+// probable prime to base a_i, that is, with n - 1 = 2^s d and x = a^d, x == 1
+// or x^(2^j) == n - 1 for some j < s. Serves the random-base rounds of
+// q.ProbablyPrime(20) in the safe-prime search (up:common/safe_prime.go).
+// R^2 mod n = Mont(2^(28 L)) by square-and-double from Mont(2),
+// a R = mont(a, R^2), a 16-entry table T[v] = a^v R in the group's LDS rows,
+// then x = a^d by Go's 4-bit fixed window (4 squarings and one table product
+// per window for every lane: the wave never diverges) and the strong check.
 template <int P, int K, int WPE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void k_mrc(const MrArgs a) {
   constexpr int L = P * K, G = 64 / P, ROWS = 17;  // table rows 0..15, work row 16
@@ -1655,20 +1284,29 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void 
   if (active && p == 0) a.ok[item] = pass ? 1 : 0;
 }
 
-// Strong Lucas test (k_lucas's ladder and checks), P lanes per candidate.
-// Per-item Montgomery constants from a thread-per-item prep (the serial
-// Horner / doubling steps), then the V ladder: every bit is one product and
-// one squaring for every lane; bits above a candidate's own top keep
-// (V_0, V_1) = (2, P) fixed (2^2 - 2 = 2, 2P - P = P), so the wave needs no
-// predication. The checks compare canonical values after leaving the
-// Montgomery domain.
+// Strong Lucas test, P lanes per candidate: Go math/big probablyPrimeLucas
+// (go:src/math/big/prime.go), the last step of ProbablyPrime. With P from
+// Baillie-OEIS method C (the smallest P >= 3 with Jacobi(P^2 - 4, n) = -1,
+// found by the caller; Q = 1) and n + 1 = 2^r s (s odd), n passes iff
+// V_s == +-2 and U_s == 0 (checked as P V_s == 2 V_{s+1}, Crandall-Pomerance
+// 3.13), or V_{2^t s} == 0 for some 0 <= t < r - 1.
+// V is built by the binary ladder V_2k = V_k^2 - 2, V_2k+1 = V_k V_k+1 - P in
+// the Montgomery domain: every bit is one product and one squaring for every
+// lane (the bit only selects where the two results go); bits above a
+// candidate's own top keep (V_0, V_1) = (2, P) fixed (2^2 - 2 = 2,
+// 2P - P = P), so the wave needs no predication. The subtractions are
+// additions of 2n - c (c = P R or 2 R, canonical): an almost-Montgomery value
+// (< 2n) may be below c, and the sum is never negative and stays < 4n. The
+// checks compare canonical values after leaving the Montgomery domain.
+// k_pprep_lucas, thread per item, does the serial Horner / doubling steps that
+// give each candidate's Montgomery constants.
 template <int L>
 __global__ __launch_bounds__(64) void k_pprep_lucas(const LucasArgs a) {
   const uint32_t i = blockIdx.x * 64u + threadIdx.x;
   if (i >= a.count) return;
   const uint32_t* nw = a.n + (size_t)i * a.n_words;
   uint32_t Nd[L], R1[L], PR[L], T[L];
-  load_candidate<L>(nw, a.n_words, true, Nd);
+  load_candidate<L>(nw, a.n_words, Nd);
   const int nbits = bitlen_digits<L>(Nd);
   r_mod<L>(Nd, nbits, R1);
   const uint32_t P = a.P[i];
@@ -1752,6 +1390,7 @@ __device__ __forceinline__ bool group_eq_small(const uint32_t (&Y)[K], uint32_t 
   return group_all<P>(e, g);
 }
 
+// the ladder and the checks of the strong Lucas test (see k_pprep_lucas)
 template <int P, int K, int WPE>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WPE))) void k_lucasc(const LucasArgs a) {
   constexpr int L = P * K, G = 64 / P;

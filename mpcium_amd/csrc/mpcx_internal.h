@@ -1,5 +1,6 @@
 // mpcx_internal.h -- kernel classes and launch arguments shared by the
-// device code (mpcx_kernels.hip) and the C-ABI host code (mpcx_api.cpp).
+// device code (mpcx_device.hpp, mpcx_mx.hpp and the .hip translation units
+// that include them) and the C-ABI host code (mpcx_api.cpp).
 #ifndef MPCX_INTERNAL_H_
 #define MPCX_INTERNAL_H_
 
@@ -51,8 +52,6 @@
 // the geometry every modulus of the class can use (L >= L_min), and the layout of
 // the class's fixed-base comb tables
 #define MPCX_FULL_GEOM(c) ((c) == 0 ? 0 : (c) == 1 ? 1 : 2)
-// 1024-bit class used by the Fermat / Miller-Rabin kernels (thread per operand)
-#define MPCX_C0_K 37
 
 // table entries per wavefront in the workspace: powers p_0..p_15 (fixed
 // window) or the odd powers x, x^3, ..., x^63 (sliding window, table[0..31]),
@@ -205,16 +204,18 @@ struct SieveArgs {
   uint32_t* out_count;       // survivor counter (zeroed before the launch)
 };
 
-// Base-2 tests of the safe-prime search (k_prime2), one candidate per lane:
-// blocks [0, f_blocks): Fermat items 2^(n-1) == 1 (mod n) over the sieve
-// survivors nf[0 .. min(count_f, *count_dev)); blocks [f_blocks, ...): strong
+// Base-2 tests of the safe-prime search (k_pprep_prime2 + k_prime2c,
+// MPCX_PRIME_P lanes per candidate): blocks [0, f_blocks): Fermat items
+// 2^(n-1) == 1 (mod n) over the sieve survivors
+// nf[0 .. min(count_f, *count_dev)); blocks [f_blocks, ...): strong
 // probable-prime-to-base-2 items over ns[0 .. count_s) (the Fermat passes' q
 // of an earlier batch riding along in the same launch). n: n_words words.
+// mpcx_launch_prime2c fills f_blocks and fp_blocks from count_f.
 struct Prime2Args {
   const uint32_t* nf;
   uint32_t count_f;
   const uint32_t* count_dev;  // optional: Fermat items = min(count_f, *count_dev)
-  uint32_t f_blocks;
+  uint32_t f_blocks;          // k_prime2c blocks (64 / MPCX_PRIME_P items) of the Fermat segment
   uint8_t* ok_f;              // optional: per-item Fermat verdicts
   // optional compaction of the Fermat passes: slot = atomicAdd(pass_count, 1),
   // pass_idx[slot] = sieve_idx[item], pass_n[slot] = the item's n_words words
@@ -226,14 +227,14 @@ struct Prime2Args {
   uint32_t count_s;
   uint8_t* ok_s;
   uint32_t n_words;
-  // cooperative kernels (k_pprep_prime2 + k_prime2c): per-item constants for
-  // the Fermat items [0, count_f) then the strong items (offset count_f)
+  // per-item constants, written by k_pprep_prime2 and read by k_prime2c: the
+  // Fermat items [0, count_f), then the strong items (offset count_f)
   uint32_t* r1;        // (count_f + count_s) x MPCX_PRIME_L digits: R mod n
   uint32_t* meta;      // (count_f + count_s) x 2: -n^-1 mod 2^28, nbits | s << 16
-  uint32_t fp_blocks;  // prep blocks (64 items) of the Fermat segment
+  uint32_t fp_blocks;  // k_pprep_prime2 blocks (64 items) of the Fermat segment
 };
 
-// Cooperative per-candidate geometries (P lanes x K digits per candidate,
+// Per-candidate geometries (P lanes x K digits per candidate,
 // L = P K digits, R = 2^(28 L) > 16 n for n < 2^1024): the base-2 tests of
 // the safe-prime step, and Miller-Rabin with arbitrary bases (latency-bound
 // batches: 16 lanes per test).
@@ -250,17 +251,18 @@ struct Prime2Args {
 
 // Strong Lucas probable-prime test (Go math/big probablyPrimeLucas, the
 // "extra strong" test with Baillie-OEIS method C parameters P, Q = 1,
-// D = P^2 - 4 with Jacobi(D, n) = -1; P is chosen by the caller).
+// D = P^2 - 4 with Jacobi(D, n) = -1; P is chosen by the caller), k_pprep_lucas
+// + k_lucasc with L = MPCX_MR_L digits per candidate (n < 2^1024) or
+// L = MPCX_LUCASW_L (the wide geometry, n < 2^2048).
 struct LucasArgs {
-  const uint32_t* n;   // count x n_words odd candidates, 5 <= n < 2^1024
+  const uint32_t* n;   // count x n_words odd candidates, 5 <= n < 2^1024 (wide: 2^2048)
   const uint32_t* P;   // count parameters (3 <= P < 2^14)
   uint8_t* ok;
   uint32_t count;
   uint32_t n_words;
-  // cooperative kernel (k_pprep_lucas + k_lucasc, MPCX_MR_L digits): per item
-  // P R, 2 R, 2n - P R, 2n - 2 R (Montgomery forms) and n0inv, nbits | r << 16
-  uint32_t* consts;  // count x 4 x MPCX_MR_L digits
-  uint32_t* meta;    // count x 2
+  // per-item constants, written by k_pprep_lucas and read by k_lucasc
+  uint32_t* consts;  // count x 4 x L digits: P R, 2 R, 2n - P R, 2n - 2 R (Montgomery forms)
+  uint32_t* meta;    // count x 2: -n^-1 mod 2^28, nbits | r << 16 (n + 1 = 2^r s)
 };
 
 // The build's CounterDRBG stream on the device: block c (32 bytes) =
@@ -273,14 +275,16 @@ struct DrbgArgs {
   uint8_t* out;
 };
 
+// Miller-Rabin to arbitrary bases (k_pprep_mr + k_mrc, MPCX_MR_P lanes per test).
 struct MrArgs {
-  const uint32_t* n;  // count x n_words odd candidates
+  const uint32_t* n;  // count x n_words odd candidates, 5 <= n < 2^1024
   const uint32_t* a;  // count x n_words bases (< 2^(32*n_words))
   uint8_t* ok;
   uint32_t count;
   uint32_t n_words;
-  uint32_t* r1;    // cooperative kernel: count x MPCX_MR_L digits (k_pprep_mr)
-  uint32_t* meta;  // count x 2
+  // per-item constants, written by k_pprep_mr and read by k_mrc
+  uint32_t* r1;    // count x MPCX_MR_L digits: R mod n
+  uint32_t* meta;  // count x 2: -n^-1 mod 2^28, nbits | s << 16 (n - 1 = 2^s d)
 };
 
 }  // namespace mpcx

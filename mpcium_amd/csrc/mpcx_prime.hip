@@ -1,7 +1,6 @@
 // mpcx_prime.hip -- launchers of the safe-prime kernels (candidate stream
-// DRBG, sieve, base-2 Fermat / strong tests, Miller-Rabin, strong Lucas;
-// thread per candidate), the shared-exponent window schedule (k_expsched) and
-// the device self-test.
+// DRBG, sieve, base-2 Fermat / strong tests, Miller-Rabin, strong Lucas), the
+// shared-exponent window schedule (k_expsched) and the device self-test.
 #ifndef MPCX_BLOCK_FENCE
 #define MPCX_BLOCK_FENCE 1  // see montmul: keeps k_prime2c within its register budget
 #endif
@@ -297,23 +296,19 @@ __global__ __launch_bounds__(256) void k_sieve(const SieveArgs a) {
 
 extern "C" {
 
-__attribute__((visibility("hidden"))) hipError_t mpcx_launch_prime2(const mpcx::Prime2Args* a, uint32_t blocks,
-                                                                   hipStream_t st) {
-  hipLaunchKernelGGL((mpcx::k_prime2<MPCX_C0_K, MPCX_WAVES_PER_EU_FERMAT>), dim3(blocks), dim3(64), 0, st, *a);
-  return hipGetLastError();
-}
-
-// cooperative base-2 tests: per-item constants, then P lanes per candidate
-// (the caller sets f_blocks = ceil(count_f / (64 / MPCX_PRIME_P)) and
-// fp_blocks = ceil(count_f / 64))
-__attribute__((visibility("hidden"))) hipError_t mpcx_launch_prime2c(const mpcx::Prime2Args* a, hipStream_t st) {
+// base-2 tests: per-item constants (thread per item), then P lanes per
+// candidate. Both kernels find where the strong items start from the Fermat
+// segment's block count, which only this launcher sets.
+__attribute__((visibility("hidden"))) hipError_t mpcx_launch_prime2c(mpcx::Prime2Args a, hipStream_t st) {
   constexpr uint32_t G = 64 / MPCX_PRIME_P;
-  const uint32_t pb = a->fp_blocks + (a->count_s + 63) / 64;
-  const uint32_t cb = a->f_blocks + (a->count_s + G - 1) / G;
-  if (pb) hipLaunchKernelGGL((mpcx::k_pprep_prime2<MPCX_PRIME_L>), dim3(pb), dim3(64), 0, st, *a);
+  a.fp_blocks = (a.count_f + 63) / 64;
+  a.f_blocks = (a.count_f + G - 1) / G;
+  const uint32_t pb = a.fp_blocks + (a.count_s + 63) / 64;
+  const uint32_t cb = a.f_blocks + (a.count_s + G - 1) / G;
+  if (pb) hipLaunchKernelGGL((mpcx::k_pprep_prime2<MPCX_PRIME_L>), dim3(pb), dim3(64), 0, st, a);
   if (cb)
     hipLaunchKernelGGL((mpcx::k_prime2c<MPCX_PRIME_P, MPCX_PRIME_K, MPCX_WAVES_PER_EU_PRIME2C>), dim3(cb), dim3(64), 0,
-                       st, *a);
+                       st, a);
   return hipGetLastError();
 }
 
@@ -345,22 +340,10 @@ __attribute__((visibility("hidden"))) hipError_t mpcx_launch_lucasc_wide(const m
   return hipGetLastError();
 }
 
-__attribute__((visibility("hidden"))) hipError_t mpcx_launch_lucas(const mpcx::LucasArgs* a, uint32_t blocks,
-                                                                  hipStream_t st) {
-  hipLaunchKernelGGL((mpcx::k_lucas<MPCX_C0_K, MPCX_WAVES_PER_EU_MR>), dim3(blocks), dim3(64), 0, st, *a);
-  return hipGetLastError();
-}
-
 __attribute__((visibility("hidden"))) hipError_t mpcx_launch_drbg(const mpcx::DrbgArgs* a, hipStream_t st) {
   const uint64_t blocks = ((a->off + a->n + 31) >> 5) - (a->off >> 5);
   if (blocks == 0) return hipSuccess;
   hipLaunchKernelGGL(mpcx::k_drbg, dim3((uint32_t)((blocks + 255) / 256)), dim3(256), 0, st, *a);
-  return hipGetLastError();
-}
-
-__attribute__((visibility("hidden"))) hipError_t mpcx_launch_mr(const mpcx::MrArgs* a, uint32_t blocks,
-                                                               hipStream_t st) {
-  hipLaunchKernelGGL((mpcx::k_mr<MPCX_C0_K, MPCX_WAVES_PER_EU_MR>), dim3(blocks), dim3(64), 0, st, *a);
   return hipGetLastError();
 }
 

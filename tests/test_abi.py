@@ -55,6 +55,16 @@ def test_fails_loudly_without_gpu(libs):
         mpcx.fermat2_batch([101])
 
 
+def test_prime_coop_is_not_an_option(libs):
+    """The thread-per-candidate prime kernels and their switch are gone:
+    "prime_coop" is an unknown option (mpcx_set_option needs no device)."""
+    from mpcium_amd import mpcx
+    with pytest.raises(mpcx.MpcxError) as ei:
+        mpcx.set_option("prime_coop", 1)
+    assert ei.value.code == mpcx.MPCX_EINVAL
+    assert "prime_coop" in str(ei.value)
+
+
 def test_missing_library_raises(monkeypatch, tmp_path):
     from mpcium_amd import mpcx
     monkeypatch.setattr(mpcx, "_LIB_PATH", str(tmp_path / "nope.so"))

@@ -1,5 +1,5 @@
 """Lane-accurate Python model of the wave-cooperative radix-2^28 Montgomery
-multiply used by mpcium_amd/csrc/mpcx_kernels.hip (design check, not shipped).
+multiply used by mpcium_amd/csrc/mpcx_device.hpp (design check, not shipped).
 G groups x P lanes x K slots; lane p of a group holds digits p*K .. p*K+K-1."""
 import random
 D = 28; M28 = (1 << D) - 1; U64 = (1 << 64) - 1
