@@ -106,7 +106,9 @@ int mpcx_device_launches(int index, uint64_t* out);
  * event pair around every launch, resolved at the lane's host wait. Writes a
  * JSON object to buf (NUL-terminated; MPCX_EINVAL if cap is too small):
  *   {"enabled":0|1,"busy_ms":B,"alg_macs":A,"kernels":[{"kind":..,"geom":g,
- *    "launches":n,"operands":n,"alg_macs":a,"kernel_ms":t},...]}
+ *    "launches":n,"operands":n,"alg_macs":a,"kernel_ms":t,"nsq_launches":n},...]}
+ * nsq_launches: of a modexp_mx entry's launches, those that ran k_modexp_nsq
+ * (option "nsq"; 0 for every other kind);
  * alg_macs: Go-equivalent work (SURVEY.md 8(d) W per exponentiation) for
  * the exponentiation kernels -- within ~5% of what they execute (same
  * squarings; 5-bit or sliding windows instead of 4-bit) -- and the executed
@@ -393,6 +395,12 @@ int mpcx_sync(void* stream);
  *                launch within 4 wavefronts per SIMD (round 5, three interleaved
  *                rounds vs 1: keygen/reshare 437.6 vs 419.7 sessions/s, signing
  *                7,110 vs 6,874 and 3,225 vs 3,039 sigs/s, profiles/r05/fbsplit).
+ *   "nsq"        1 (default) or 0: a single k_modexp_mx batch with a shared
+ *                exponent, no multiplier and a modulus that is a perfect square
+ *                N^2 (Paillier's r^N mod N^2) runs k_modexp_nsq: N-adic pairs,
+ *                two 76-digit products and two reductions mod N per squaring
+ *                (DESIGN.md 5.2h). Same results; mpcx_kernel_stats counts such
+ *                launches in the modexp_mx entry's "nsq_launches".
  *   "mx"         1 (default), 0 or 2: batches of the 4096-bit main geometry
  *                (>= "mx_min" operands, default 2048) run k_modexp_mx, the
  *                Montgomery reduction on the i8 matrix cores (round 5: config 2
@@ -436,9 +444,9 @@ int mpcx_sync(void* stream);
  *                with an event pair for mpcx_kernel_stats.
  * Environment, read at mpcx_init / mpcx_init_devices: MPCX_LANES (1..8,
  * default 6: execution lanes per device), MPCX_GEOM_POLICY, MPCX_NARROW_ROUNDS,
- * MPCX_FB_WINDOW, MPCX_MX, MPCX_MX_STEP, MPCX_GEOM_TPUT. */
+ * MPCX_FB_WINDOW, MPCX_MX, MPCX_NSQ, MPCX_MX_STEP, MPCX_GEOM_TPUT. */
 int mpcx_set_option(const char* key, int value);
-/* Current value of "mx", "mx_min", "mx_seg_min", "mx_step", "geom_tput",
+/* Current value of "mx", "nsq", "mx_min", "mx_seg_min", "mx_step", "geom_tput",
  * "geom_policy", "sched_width", "fixed_window", "fb_split" or "lanes"
  * (benchmarks record which kernel path ran). */
 int mpcx_get_option(const char* key, int* value);
@@ -451,6 +459,14 @@ int mpcx_get_option(const char* key, int* value);
  * reversed radix-2^7 digit strings (23,040 or 13,824 bytes). Host-only (no
  * device needed); for tests and tools. */
 int mpcx_mx_tables(const uint32_t* m_words, uint32_t m_len, uint32_t L, uint8_t* out, size_t cap);
+
+/* The constants of k_modexp_nsq (x^e mod N^2 on N-adic pairs, option "nsq") for an
+ * odd modulus m of the 4096-bit class: *is_square = 1 and out = 380 radix-2^28
+ * digits (N = sqrt(m), then a0, b0, a1, b1 with a0 + b0 N = 2^4256 and
+ * a1 + b1 N = 2^6328 mod m, 76 digits each) followed by mpcx_mx_tables(N, 76) as
+ * 3,456 words -- or *is_square = 0 and out untouched when m is not the square of
+ * an N of 1025..2048 bits. Host-only (no device needed); for tests and tools. */
+int mpcx_nsq_consts(const uint32_t* m_words, uint32_t m_len, uint32_t* out, size_t cap_words, int* is_square);
 
 /* Kernel-class geometry of a modulus (for benchmarks and roofline math):
  * digits L (radix 2^28), lanes per operand P, digits per lane K, operands per

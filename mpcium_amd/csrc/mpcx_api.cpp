@@ -84,6 +84,13 @@ struct mpcx_modulus_s {
   // k_modexp_mx (4096-bit class): Toeplitz fragments of m'' and m, built on first use
   std::vector<uint8_t> mx_host;
   uint8_t* d_mx[kMaxDevices] = {};
+  // k_modexp_nsq (m = N^2): found out and built at the first launch that could take
+  // it (nsq_state 0: not yet looked; 1: m is a perfect square; -1: it is not).
+  // nsq_host: N's digits and the entry constants (MPCX_NSQ_CONST_DIGITS), then N's
+  // Toeplitz tables in MxN2's shape, as words
+  int nsq_state = 0;
+  std::vector<uint32_t> nsq_host;
+  uint32_t* d_nsq[kMaxDevices] = {};
 };
 
 struct mpcx_fixedbase_s {
@@ -124,6 +131,10 @@ bool g_dup_device = false;               // mpcx_set_option("duplicate_device", 
 #define MPCX_MX_DEFAULT 1
 #endif
 int g_mx = MPCX_MX_DEFAULT;              // mpcx_set_option("mx", 1): geometry-2 batches reduce on the matrix cores
+#ifndef MPCX_NSQ_DEFAULT
+#define MPCX_NSQ_DEFAULT 1
+#endif
+int g_nsq = MPCX_NSQ_DEFAULT;            // mpcx_set_option("nsq", 1): a k_modexp_mx batch with m = N^2 and a shared exponent runs k_modexp_nsq
 uint32_t g_mx_min = 2048;                // mpcx_set_option("mx_min", n): smallest batch for k_modexp_mx
 uint32_t g_mx_seg_min = 64;              // mpcx_set_option("mx_seg_min", n): smallest segment of a k_modexp_multi_mx launch (round 6: 64 vs 256, profiles/r06/segmin*)
 double g_mx_step = 0.81;                 // mpcx_set_option("mx_step", 100x): k_modexp_mx's wave-round time / k_modexp's (100: model ignores mx)
@@ -166,6 +177,7 @@ struct Lane {
     int geom;
     uint32_t ops;
     double alg;
+    bool nsq = false;  // a modexp_mx launch that ran k_modexp_nsq
   };
   std::vector<KEv> kev_free;
   std::vector<KPend> kpend;
@@ -300,6 +312,7 @@ void launch_log(const char* kind, int geom, uint32_t count, uint32_t mod_bits, u
 std::atomic<bool> g_kstats{false};
 struct KAgg {
   uint64_t launches = 0, ops = 0;
+  uint64_t nsq = 0;  // of the launches: k_modexp_nsq's (kind modexp_mx only)
   double alg = 0.0, ms = 0.0;
 };
 std::mutex g_kmu;
@@ -341,7 +354,8 @@ int kstat_begin(Lane& l) {
   return (int)l.kpend.size() - 1;
 }
 
-void kstat_end(Lane& l, int slot, const Device& d, int dev, const char* kind, int geom, uint32_t ops, double alg) {
+void kstat_end(Lane& l, int slot, const Device& d, int dev, const char* kind, int geom, uint32_t ops, double alg,
+               bool nsq = false) {
   if (slot < 0) return;
   Lane::KPend& p = l.kpend[(size_t)slot];
   if (!d.kref || hipEventRecord(p.ev.b, l.st) != hipSuccess) {
@@ -355,6 +369,7 @@ void kstat_end(Lane& l, int slot, const Device& d, int dev, const char* kind, in
   p.geom = geom;
   p.ops = ops;
   p.alg = alg;
+  p.nsq = nsq;
 }
 
 // work of a launch whose operand count is known only after it ran (the
@@ -376,6 +391,7 @@ void kstat_resolve(Lane& l) {
         hipEventElapsedTime(&t0, p.ref, p.ev.a) == hipSuccess) {
       KAgg& a = g_kagg[{p.kind, p.geom}];
       a.launches += 1;
+      a.nsq += p.nsq ? 1 : 0;
       a.ops += p.ops;
       a.alg += p.alg;
       a.ms += ms;
@@ -481,6 +497,8 @@ static bool mx_dims(uint32_t L, MxDims* o) {
     *o = {mpcx::MxG2::N7, mpcx::MxG2::D, mpcx::MxG2::TAB_STRIDE, mpcx::MxG2::IMG_BYTES};
   } else if (L == mpcx::MxG5::L) {
     *o = {mpcx::MxG5::N7, mpcx::MxG5::D, mpcx::MxG5::TAB_STRIDE, mpcx::MxG5::IMG_BYTES};
+  } else if (L == mpcx::MxN2::L) {
+    *o = {mpcx::MxN2::N7, mpcx::MxN2::D, mpcx::MxN2::TAB_STRIDE, mpcx::MxN2::IMG_BYTES};
   } else {
     return false;
   }
@@ -539,6 +557,104 @@ static void mx_tables(const std::vector<uint32_t>& m, uint32_t L, std::vector<ui
   };
   fill(n2, out.data());
   fill(n1, out.data() + dm.img / 2);
+}
+
+// ---- k_modexp_nsq constants (mpcx_device.hpp): is m a perfect square N^2, and
+// the pairs (a, b), a + b N = c mod m with a, b < N, of the entry constants.
+// (The bignum class of libmpcx_host is not linked into this library; these run
+// once per modulus on word vectors.)
+static void trim(std::vector<uint32_t>& x) {
+  while (x.size() > 1 && x.back() == 0) x.pop_back();
+}
+// floor(sqrt(m)) bit by bit (shift and subtract), *exact: m is its square
+static std::vector<uint32_t> isqrt_words(const std::vector<uint32_t>& m, bool* exact) {
+  const size_t n = m.size();
+  std::vector<uint32_t> rem(m), res(n, 0), t(n);
+  auto bit_of = [&](uint32_t b) { return std::pair<size_t, uint32_t>(b >> 5, 1u << (b & 31)); };
+  for (int b = (int)((bit_length(m) - 1) & ~1u); b >= 0; b -= 2) {
+    // t = res + 2^b (bit b of res is clear: res only has bits above b)
+    t = res;
+    const auto [wi, msk] = bit_of((uint32_t)b);
+    t[wi] |= msk;
+    bool ge = true;
+    for (int i = (int)n - 1; i >= 0; --i)
+      if (rem[i] != t[i]) {
+        ge = rem[i] > t[i];
+        break;
+      }
+    uint32_t c = 0;  // res >>= 1
+    for (int i = (int)n - 1; i >= 0; --i) {
+      const uint32_t nc = res[i] & 1u;
+      res[i] = (res[i] >> 1) | (c << 31);
+      c = nc;
+    }
+    if (ge) {
+      uint64_t br = 0;
+      for (size_t i = 0; i < n; ++i) {
+        const uint64_t d = (uint64_t)rem[i] - t[i] - br;
+        rem[i] = (uint32_t)d;
+        br = (d >> 63) & 1;
+      }
+      res[wi] |= msk;
+    }
+  }
+  *exact = true;
+  for (uint32_t w : rem) *exact = *exact && w == 0;
+  trim(res);
+  return res;
+}
+// x = q n + r by shift and subtract (x < n^2: q, r < n)
+static void divmod_words(const std::vector<uint32_t>& x, const std::vector<uint32_t>& n, std::vector<uint32_t>* q,
+                         std::vector<uint32_t>* r) {
+  const size_t k = n.size();
+  std::vector<uint32_t> rem(k + 1, 0), nn(n);
+  nn.push_back(0);
+  q->assign(x.size(), 0);
+  for (int b = (int)(32 * x.size()) - 1; b >= 0; --b) {
+    uint32_t c = (x[(size_t)b >> 5] >> (b & 31)) & 1u;
+    for (size_t i = 0; i <= k; ++i) {
+      const uint32_t nc = rem[i] >> 31;
+      rem[i] = (rem[i] << 1) | c;
+      c = nc;
+    }
+    if (geq(rem, nn)) {
+      uint64_t br = 0;
+      for (size_t i = 0; i <= k; ++i) {
+        const uint64_t d = (uint64_t)rem[i] - nn[i] - br;
+        rem[i] = (uint32_t)d;
+        br = (d >> 63) & 1;
+      }
+      (*q)[(size_t)b >> 5] |= 1u << (b & 31);
+    }
+  }
+  rem.resize(k);
+  *r = rem;
+}
+// m a perfect square N^2 of the 4096-bit class: out <- N's digits, the pairs of R^2
+// and 2^MPCX_NSQ_SPLIT_BITS R^2 mod m (R = 2^(28 MxN2::L)), N's Toeplitz tables
+static bool nsq_build(const std::vector<uint32_t>& m, std::vector<uint32_t>& out) {
+  constexpr uint32_t L = mpcx::MxN2::L;
+  if ((m[0] & 7u) != 1u) return false;  // an odd square is 1 mod 8
+  bool exact = false;
+  const std::vector<uint32_t> n = isqrt_words(m, &exact);
+  // R = 2^2128 > 2^80 N keeps every intermediate of the pair product in 76 digits
+  if (!exact || bit_length(n) > 2048 || bit_length(n) < 1025) return false;
+  out.clear();
+  const auto nd = to_digits(n, L);
+  out.insert(out.end(), nd.begin(), nd.end());
+  for (uint32_t extra : {0u, (uint32_t)MPCX_NSQ_SPLIT_BITS}) {
+    std::vector<uint32_t> c = pow2_mod(2 * kDigitBits * L + extra, m), a, b;
+    divmod_words(c, n, &b, &a);
+    const auto ad = to_digits(a, L), bd = to_digits(b, L);
+    out.insert(out.end(), ad.begin(), ad.end());
+    out.insert(out.end(), bd.begin(), bd.end());
+  }
+  std::vector<uint8_t> img;
+  mx_tables(n, L, img);
+  const size_t at = out.size();
+  out.resize(at + img.size() / 4);
+  std::memcpy(out.data() + at, img.data(), img.size());
+  return true;
 }
 
 hipError_t mpcx_launch_modexp(int geom, const mpcx::ModexpArgs* a, uint32_t waves, hipStream_t st) {
@@ -1085,6 +1201,28 @@ int mx_const(mpcx_mod_t mod, int di, const uint8_t** out) {
   return MPCX_OK;
 }
 
+// k_modexp_nsq's constants of mod on bound device di, *out = nullptr when mod is no
+// perfect square (looked at once, at the first launch that asks)
+int nsq_const(mpcx_mod_t mod, int di, const uint32_t** out) {
+  std::lock_guard<std::mutex> lk(mod->mu);
+  *out = nullptr;
+  if (mod->nsq_state == 0) mod->nsq_state = nsq_build(mod->m, mod->nsq_host) ? 1 : -1;
+  if (mod->nsq_state < 0) return MPCX_OK;
+  if (!mod->d_nsq[di]) {
+    uint32_t* p = nullptr;
+    const size_t bytes = mod->nsq_host.size() * sizeof(uint32_t);
+    hipError_t e = hipMalloc((void**)&p, bytes);
+    if (e != hipSuccess) return fail(MPCX_ENOMEM, "hipMalloc(nsq constants): %s", hipGetErrorString(e));
+    if (int rc = copy_sync(p, mod->nsq_host.data(), bytes, hipMemcpyHostToDevice, nullptr)) {
+      (void)hipFree(p);
+      return rc;
+    }
+    mod->d_nsq[di] = p;
+  }
+  *out = mod->d_nsq[di];
+  return MPCX_OK;
+}
+
 int fb_table(mpcx_fb_t fb, int di, const uint32_t** out) {
   std::lock_guard<std::mutex> lk(fb->mu);
   if (!fb->d_table[di]) {
@@ -1490,6 +1628,8 @@ int mpcx_get_option(const char* key, int* value) {
   std::lock_guard<std::mutex> lk(g_mu);
   if (std::strcmp(key, "mx") == 0) {
     *value = g_mx;
+  } else if (std::strcmp(key, "nsq") == 0) {
+    *value = g_nsq;
   } else if (std::strcmp(key, "mx_min") == 0) {
     *value = (int)g_mx_min;
   } else if (std::strcmp(key, "mx_seg_min") == 0) {
@@ -1542,6 +1682,11 @@ int mpcx_set_option(const char* key, int value) {
     // 2: the 2048-bit lane-pair geometry's as well
     if (value < 0 || value > 2) return fail(MPCX_EINVAL, "mx %d not 0, 1 or 2", value);
     g_mx = value;
+  } else if (std::strcmp(key, "nsq") == 0) {
+    // 1: a single k_modexp_mx batch with a shared exponent and a perfect-square modulus N^2
+    // runs on N-adic pairs (k_modexp_nsq); 0: k_modexp_mx
+    if (value < 0 || value > 1) return fail(MPCX_EINVAL, "nsq %d not 0 or 1", value);
+    g_nsq = value;
   } else if (std::strcmp(key, "mx_min") == 0) {
     if (value < 1) return fail(MPCX_EINVAL, "mx_min %d < 1", value);
     g_mx_min = (uint32_t)value;
@@ -1612,6 +1757,8 @@ static void read_env_options() {
   if (fw) g_fb_window = std::max(4, std::min(MPCX_FB_MAX_WINDOW_BITS, std::atoi(fw)));
   const char* mx = std::getenv("MPCX_MX");  // geometry-2 batches on k_modexp_mx
   if (mx) g_mx = std::max(0, std::min(2, std::atoi(mx)));
+  const char* nq = std::getenv("MPCX_NSQ");  // N^2 batches with a shared exponent on k_modexp_nsq
+  if (nq) g_nsq = std::max(0, std::min(1, std::atoi(nq)));
   const char* ms = std::getenv("MPCX_MX_STEP");  // x100, the launch-time model's k_modexp_mx step (A/B runs)
   if (ms) g_mx_step = std::max(10, std::min(200, std::atoi(ms))) / 100.0;
   const char* gt = std::getenv("MPCX_GEOM_TPUT");  // x100, the launch-time model's GPU-share weight
@@ -1688,10 +1835,10 @@ int mpcx_kernel_stats(char* buf, size_t cap, int reset) {
       alg += kv.second.alg;
       std::snprintf(line, sizeof line,
                     "%s{\"kind\":\"%s\",\"geom\":%d,\"launches\":%llu,\"operands\":%llu,\"alg_macs\":%.6e,"
-                    "\"kernel_ms\":%.4f}",
+                    "\"kernel_ms\":%.4f,\"nsq_launches\":%llu}",
                     ks.empty() ? "" : ",", kv.first.first.c_str(), kv.first.second,
                     (unsigned long long)kv.second.launches, (unsigned long long)kv.second.ops, kv.second.alg,
-                    kv.second.ms);
+                    kv.second.ms, (unsigned long long)kv.second.nsq);
       ks += line;
     }
     std::snprintf(line, sizeof line, "{\"enabled\":%d,\"busy_ms\":%.4f,\"alg_macs\":%.6e,\"kernels\":[",
@@ -1800,6 +1947,7 @@ int mpcx_modulus_release(mpcx_mod_t mod) {
   for (int i = 0; i < n && i < kMaxDevices; ++i) {
     if (mod->d_const[i] && bind(g_devs[i]) == MPCX_OK) (void)hipFree(mod->d_const[i]);
     if (mod->d_mx[i] && bind(g_devs[i]) == MPCX_OK) (void)hipFree(mod->d_mx[i]);
+    if (mod->d_nsq[i] && bind(g_devs[i]) == MPCX_OK) (void)hipFree(mod->d_nsq[i]);
   }
   delete mod;
   return MPCX_OK;
@@ -1808,7 +1956,7 @@ int mpcx_modulus_release(mpcx_mod_t mod) {
 int mpcx_mx_tables(const uint32_t* m_words, uint32_t m_len, uint32_t L, uint8_t* out, size_t cap) {
   if (!m_words || !out || m_len == 0) return fail(MPCX_EINVAL, "null modulus or output");
   MxDims dm{};
-  if (!mx_dims(L, &dm)) return fail(MPCX_EINVAL, "L %u is not an MX geometry's (148 or 74)", L);
+  if (!mx_dims(L, &dm)) return fail(MPCX_EINVAL, "L %u is not an MX geometry's (148, 76 or 74)", L);
   if (cap < dm.img) return fail(MPCX_EINVAL, "mx tables need %u bytes", dm.img);
   std::vector<uint32_t> m(m_words, m_words + m_len);
   while (m.size() > 1 && m.back() == 0) m.pop_back();
@@ -1818,6 +1966,21 @@ int mpcx_mx_tables(const uint32_t* m_words, uint32_t m_len, uint32_t L, uint8_t*
   std::vector<uint8_t> t;
   mx_tables(m, L, t);
   std::memcpy(out, t.data(), dm.img);
+  return MPCX_OK;
+}
+
+int mpcx_nsq_consts(const uint32_t* m_words, uint32_t m_len, uint32_t* out, size_t cap_words, int* is_square) {
+  if (!m_words || !is_square || m_len == 0) return fail(MPCX_EINVAL, "null modulus or output");
+  std::vector<uint32_t> m(m_words, m_words + m_len);
+  while (m.size() > 1 && m.back() == 0) m.pop_back();
+  if ((m[0] & 1u) == 0 || class_for_bits(bit_length(m)) != 2)
+    return fail(MPCX_EINVAL, "nsq constants need an odd modulus of the 4096-bit class");
+  std::vector<uint32_t> c;
+  *is_square = nsq_build(m, c) ? 1 : 0;
+  if (*is_square) {
+    if (!out || cap_words < c.size()) return fail(MPCX_EINVAL, "nsq constants need %zu words", c.size());
+    std::memcpy(out, c.data(), c.size() * sizeof(uint32_t));
+  }
   return MPCX_OK;
 }
 
@@ -1873,24 +2036,35 @@ static int modexp_enqueue(int di, Lane& lane, mpcx_mod_t mod, uint32_t count, co
   const uint32_t waves = (count + G - 1) / G;
   // a shared exponent's sliding-window schedule lives after the tables
   const bool use_sched = exp_shared && exp_bits > 0 && g_sched_width > 0;
-  const size_t sched_off = (size_t)waves * MPCX_TABLE_ENTRIES * K * 64u;
+  const bool mx = runs_on_mx(geom, count, count, false);
+  // m = N^2 with a shared exponent and no multiplier: k_modexp_nsq (N-adic pairs,
+  // the same wavefront split as geometry 2) in place of k_modexp_mx
+  const uint32_t* dnsq = nullptr;
+  if (g_nsq && mx && geom == 2 && use_sched && !d_muls && (rc = nsq_const(mod, di, &dnsq))) return rc;
+  const size_t sched_off = (size_t)waves * MPCX_TABLE_ENTRIES * (dnsq ? (uint32_t)MPCX_NSQ_TABLE_SLOTS : K) * 64u;
   const size_t ws_words = sched_off + (use_sched ? MPCX_SCHED_WORDS(32u * exp_words) : 0);
   if ((rc = ensure_workspace(lane, ws_words * sizeof(uint32_t)))) return rc;
   uint32_t* sched = use_sched ? lane.ws + sched_off : nullptr;
   if (use_sched && (rc = launch_expsched(d_exps, exp_words, sched, lane.st))) return rc;
-  const bool mx = runs_on_mx(geom, count, count, false);
   const uint8_t* mx_img = nullptr;
-  if (mx && (rc = mx_const(mod, di, &mx_img))) return rc;
-  const mpcx::ModexpArgs a =
+  if (dnsq) {
+    mx_img = reinterpret_cast<const uint8_t*>(dnsq + MPCX_NSQ_CONST_DIGITS);
+  } else if (mx && (rc = mx_const(mod, di, &mx_img))) {
+    return rc;
+  }
+  mpcx::ModexpArgs a =
       modexp_args(mod, geom, dconst, count, d_bases, base_words, d_exps, exp_words, d_muls, mul_words, d_out,
                   out_words, lane.ws, exp_bits, exp_shared, sched, mx_img, waves);
+  a.nsq = dnsq;
   const char* kind = mx ? "modexp_mx" : "modexp";
   const int ks = kstat_begin(lane);
   hipError_t e = mpcx_launch_modexp(geom, &a, waves, lane.st);
   if (e != hipSuccess) return hip_fail(e, "launch k_modexp");
   dev.launches.fetch_add(1, std::memory_order_relaxed);
   const double alg = alg_macs >= 0 ? alg_macs : go_macs(mod->bits, a.exp_bits) * count;
-  kstat_end(lane, ks, dev, di, kind, geom, count, alg);
+  // k_modexp_nsq stays under the kind of the kernel it stands in for (the plans and
+  // rooflines read "modexp_mx"); the entry's nsq_launches tells the two apart
+  kstat_end(lane, ks, dev, di, kind, geom, count, alg, dnsq != nullptr);
   launch_log(kind, geom, count, mod->bits, a.exp_bits, alg);
   return MPCX_OK;
 }

@@ -668,6 +668,278 @@ __global__ __launch_bounds__(64 * MX_WG) __attribute__((amdgpu_waves_per_eu(WPE)
   modexp_wave<P, K, G, true>(a, blockIdx.x * MX_WG + (threadIdx.x >> 6));
 }
 
+#ifndef MX_PROF
+// x^e mod N^2 for a shared exponent e and a public N (Paillier: config 2's r^N mod
+// N^2), on N-adic pairs: y is held as (u, v) with y R = u + v N (mod N^2),
+// R = 2^2128, u and v within 2^-9 of (N/2, 3N/2) as 76 digits each (a quad of 19, as
+// geometry 1), and a product is pairmul_mx (mpcx_mx.hpp): one 76-digit squaring and
+// one 76-digit product per squaring instead of a 148-digit squaring, and two
+// reductions mod N (R = 2^2128) instead of one mod N^2 (R = 2^4144). DESIGN.md 5.2h.
+//  * entry: x = x0 + x1 2^2072 -> (x0, 0) x (a0, b0) + (x1, 0) x (a1, b1), the pairs of
+//    R^2 and 2^2072 R^2 mod N^2 (a.nsq), added componentwise: u, v < 3.01 N;
+//  * the schedule of k_expsched as in modexp_wave, odd powers as pairs in the table;
+//  * exit: (u, v) x (1, 0) = (a, b) with y = a + b N mod N^2; a + b N < 2 N^2 is formed
+//    by one more product loop and N^2 (a.nd, geometry 2's digits) subtracted once if
+//    it is not below it.
+// ONE call site per pairmul_mx variant, as modexp_wave's.
+__device__ __forceinline__ void modexp_nsq_wave(const ModexpArgs& a, const uint32_t blk) {
+  using S = MxN2;
+  constexpr int P = S::P, K = S::K, L = S::L, G = S::G, ROW = S::ROW;
+  constexpr int KT = MPCX_NSQ_TABLE_SLOTS;
+  // per wave: the row sets a and b, +4 (the product loop reads one past a row), the
+  // product loop's trash slots
+  constexpr int WAVE_WORDS = 2 * G * ROW + 4 + ((64 + L + 3) / 4) * 4;
+  constexpr int WAVES_OFF = S::IMG_BYTES / 4 + L + 4;
+  __shared__ __attribute__((aligned(16))) uint32_t lds_all[WAVES_OFF + MPCX_NSQ_WG * WAVE_WORDS];
+  {
+    const uint32_t* img = static_cast<const uint32_t*>(a.mx_img);
+    for (int i = (int)threadIdx.x; i < S::IMG_BYTES / 4; i += 64 * MPCX_NSQ_WG) lds_all[i] = img[i];
+    for (int i = (int)threadIdx.x; i < L; i += 64 * MPCX_NSQ_WG) lds_all[S::IMG_BYTES / 4 + i] = a.nsq[i];
+    __syncthreads();
+    if (blk >= a.nwaves) return;  // the last workgroup's spare wavefronts
+  }
+  const int lane = (int)(threadIdx.x & 63u);
+  const int g = lane / P, p = lane % P;
+  const uint32_t op = blk * G + (uint32_t)g;
+  const bool active = op < a.count;
+  const uint32_t* md = lds_all + S::IMG_BYTES / 4;  // N's digits
+  uint32_t* ra = lds_all + WAVES_OFF + (blk % MPCX_NSQ_WG) * WAVE_WORDS;
+  uint32_t* rb = ra + G * ROW;
+  uint32_t* tr = ra + 2 * G * ROW + 4 + lane;
+  uint32_t* ga = ra + g * ROW;
+  uint32_t* gb = rb + g * ROW;
+  const MxConsts mxc = mx_consts<S>(reinterpret_cast<const uint8_t*>(lds_all), lane);
+  uint32_t* out = a.out + (size_t)op * a.out_words;
+
+  const uint32_t top = __builtin_amdgcn_readfirstlane(a.sched[MPCX_SCHED_TOP]);
+  if (top == MPCX_SCHED_NONE) {  // e = 0
+    if (active)
+      for (uint32_t w = (uint32_t)p; w < a.out_words; w += P) out[w] = w == 0 ? 1u : 0u;
+    return;
+  }
+  const uint32_t T = __builtin_amdgcn_readfirstlane(a.sched[MPCX_SCHED_TN]);
+  const uint32_t nsteps = __builtin_amdgcn_readfirstlane(a.sched[MPCX_SCHED_N]);
+
+  uint32_t U[K], V[K];
+  uint32_t* tbl = a.table + (size_t)blk * MPCX_TABLE_ENTRIES * KT * 64u;
+  const auto tbl_rsrc =
+      __builtin_amdgcn_make_buffer_rsrc(tbl, (short)0, (int)(MPCX_TABLE_ENTRIES * KT * 64u * 4u), 0x00020000);
+  auto tbl_store = [&](uint32_t e) __attribute__((always_inline)) {
+    const int voff = lane * 4 + (int)(e * KT * 256u);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      __builtin_amdgcn_raw_buffer_store_b32(U[k], tbl_rsrc, voff, k * 256, 0);
+      __builtin_amdgcn_raw_buffer_store_b32(V[k], tbl_rsrc, voff, (K + k) * 256, 0);
+    }
+  };
+  auto tbl_load = [&](uint32_t e, uint32_t (&u)[K], uint32_t (&v)[K]) __attribute__((always_inline)) {
+    const int voff = lane * 4 + (int)(e * KT * 256u);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      u[k] = __builtin_amdgcn_raw_buffer_load_b32(tbl_rsrc, voff, k * 256, 0);
+      v[k] = __builtin_amdgcn_raw_buffer_load_b32(tbl_rsrc, voff, (K + k) * 256, 0);
+    }
+  };
+  // the multiplier rows: a table entry, a pair of a.nsq's constants, 2u twice, (1, 0)
+  auto stage_entry = [&](uint32_t e) __attribute__((always_inline)) {
+    uint32_t u[K], v[K];
+    tbl_load(e, u, v);
+    lds_store_digits<K>(ga, p, u);
+    lds_store_digits<K>(gb, p, v);
+  };
+  auto stage_const = [&](const uint32_t* src) __attribute__((always_inline)) {
+    asm volatile("" : "+s"(src));
+    int pp = p;
+    asm volatile("" : "+v"(pp));
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      ga[pp * K + k] = src[pp * K + k];
+      gb[pp * K + k] = src[L + pp * K + k];
+    }
+  };
+  auto stage_sqr = [&]() __attribute__((always_inline)) {
+    lds_store_sqr<K>(ga, p, U);
+    lds_store_sqr<K>(gb, p, U);
+  };
+  auto stage_unit = [&](uint32_t* row1, uint32_t* row0) __attribute__((always_inline)) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      row1[p * K + k] = (p == 0 && k == 0) ? 1u : 0u;
+      row0[p * K + k] = 0u;
+    }
+  };
+  // (U, V) <- (74 digits of the base from digit d0 on, 0); inactive operands: 0
+  auto load_half = [&](uint32_t d0) __attribute__((always_inline)) {
+    const uint32_t* src = a.base;
+    asm volatile("" : "+s"(src));
+    int pp = p;
+    asm volatile("" : "+v"(pp));
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      const uint32_t d = (uint32_t)(pp * K + k);
+      const uint32_t bit = (d0 + d) * DB;
+      const uint32_t w = bit >> 5, sh = bit & 31u;
+      uint64_t v = 0;
+      if (active && d < (uint32_t)MPCX_NSQ_SPLIT_DIGITS) {
+        const uint32_t* x = src + (size_t)op * a.base_words;
+        const uint32_t lo = w < a.base_words ? x[w] : 0u;
+        const uint32_t hi = (w + 1) < a.base_words ? x[w + 1] : 0u;
+        v = ((uint64_t)hi << 32) | lo;
+      }
+      U[k] = (uint32_t)(v >> sh) & M28;
+      V[k] = 0u;
+    }
+  };
+
+  enum { ST_IN0, ST_IN1, ST_TSQ, ST_STAB, ST_EXP, ST_OUT };
+  int st = ST_IN0;
+  uint32_t idx = 1, sq_left = 0;
+  int pend = -1, restage = -1;
+  bool sqr = false;
+  stage_const(a.nsq + L);
+  load_half(0);
+  wave_lds_fence();
+  for (;;) {
+    if (restage != -1) {
+      stage_entry((uint32_t)restage);
+      restage = -1;
+      wave_lds_fence();
+    }
+    if (sqr) {
+      pairmul_mx<S, true>(U, V, ra, rb, tr, md, mxc, lane);
+    } else {
+      pairmul_mx<S, false>(U, V, ra, rb, tr, md, mxc, lane);
+    }
+    sqr = false;
+    wave_lds_fence();
+    bool start_exp = false, run_exp = false;
+    if (st == ST_IN0) {
+      tbl_store(0);
+      stage_const(a.nsq + 3 * L);
+      load_half(MPCX_NSQ_SPLIT_DIGITS);
+      st = ST_IN1;
+    } else if (st == ST_IN1) {
+      // the pair of x: the two halves' pairs added, one carry pass (digits <= 2^28 + 2)
+      uint32_t u0[K], v0[K];
+      tbl_load(0, u0, v0);
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        U[k] += u0[k];
+        V[k] += v0[k];
+      }
+      carry_pass32<P, K>(U);
+      carry_pass32<P, K>(V);
+      tbl_store(0);
+      if (T > 0u) {
+        stage_sqr();
+        sqr = true;
+        st = ST_TSQ;
+      } else {
+        start_exp = true;
+      }
+    } else if (st == ST_TSQ) {
+      lds_store_digits<K>(ga, p, U);  // the odd-power chain multiplies by x^2
+      lds_store_digits<K>(gb, p, V);
+      tbl_store(MPCX_SQ_ENTRY);
+      tbl_load(0, U, V);
+      st = ST_STAB;
+      idx = 1;
+    } else if (st == ST_STAB) {
+      tbl_store(idx);
+      if (idx < T) {
+        restage = MPCX_SQ_ENTRY;
+        ++idx;
+      } else {
+        start_exp = true;
+      }
+    } else if (st == ST_EXP) {
+      run_exp = true;
+    } else {
+      break;  // ST_OUT done
+    }
+    if (start_exp) {
+      tbl_load(top, U, V);
+      st = ST_EXP;
+      idx = 0;
+      run_exp = true;
+    }
+    if (run_exp) {
+      for (;;) {
+        if (sq_left) {
+          --sq_left;
+          stage_sqr();
+          sqr = true;
+          break;
+        }
+        if (pend >= 0) {
+          stage_entry((uint32_t)pend);
+          pend = -1;
+          break;
+        }
+        if (idx == nsteps) {
+          st = ST_OUT;
+          stage_unit(ga, gb);
+          break;
+        }
+        const uint32_t s = __builtin_amdgcn_readfirstlane(a.sched[MPCX_SCHED_STEPS + idx]);
+        sq_left = s >> 8;
+        pend = (s & 0xFFu) == 0xFFu ? -1 : (int)(s & 0xFFu);
+        ++idx;
+      }
+    }
+    wave_lds_fence();
+  }
+
+  // a + b N = U x (row b = 1) + V x (row a = N): low digits -> row b, high -> V -> row a
+  stage_unit(gb, ga);
+#pragma unroll
+  for (int k = 0; k < K; ++k) ga[p * K + k] = md[p * K + k];
+  wave_lds_fence();
+  mx_product2<P, K>(U, V, ga, gb, tr, p);
+  canonicalize<P, K>(V);
+  wave_lds_fence();
+  lds_store_digits<K>(ga, p, V);
+  wave_lds_fence();
+  auto digit = [&](uint32_t d) __attribute__((always_inline)) -> uint32_t {
+    return d < (uint32_t)L ? gb[d] : (d < 2u * L ? ga[d - L] : 0u);
+  };
+  if (p == 0) {  // one lane per operand, once per exponentiation: y - N^2 if y >= N^2
+    constexpr uint32_t L2 = (uint32_t)MPCX_GEOM_L(2);
+    int c = 0;
+    for (int d = 2 * L - 1; d >= 0; --d) {
+      const uint32_t x = digit((uint32_t)d), m = (uint32_t)d < L2 ? a.nd[d] : 0u;
+      if (c == 0 && x != m) c = x > m ? 1 : -1;
+    }
+    if (c >= 0) {
+      uint32_t borrow = 0;
+      for (uint32_t d = 0; d < 2u * L; ++d) {
+        const uint32_t m = d < L2 ? a.nd[d] : 0u;
+        const uint32_t t = digit(d) - m - borrow;
+        borrow = t >> 31;
+        (d < (uint32_t)L ? gb[d] : ga[d - L]) = t & M28;
+      }
+    }
+  }
+  wave_lds_fence();
+  if (active) {
+    for (uint32_t w = (uint32_t)p; w < a.out_words; w += P) {
+      const uint32_t bit = w * 32u;
+      const uint32_t d0 = bit / DB, s0 = bit % DB;
+      const uint64_t lo = digit(d0), hi = digit(d0 + 1u);
+      out[w] = (uint32_t)((lo | (hi << DB)) >> s0);
+    }
+  }
+}
+
+// MPCX_NSQ_WG wavefronts per workgroup share N's tables; the wave index goes through
+// readfirstlane so that the window table's buffer descriptor is provably uniform
+template <int WPE>
+__global__ __launch_bounds__(64 * MPCX_NSQ_WG) __attribute__((amdgpu_waves_per_eu(WPE))) void k_modexp_nsq(
+    const ModexpArgs a) {
+  modexp_nsq_wave(a, blockIdx.x * MPCX_NSQ_WG + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
+}
+#endif  // MX_PROF
+
 // Several batches of one modulus class in one launch (mpcx_modexp_multi_batch:
 // different moduli, shared or per-operand exponents, multipliers): segment s
 // owns wavefronts [first[s], first[s+1]) and its own ModexpArgs (constants,

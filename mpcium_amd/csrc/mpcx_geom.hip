@@ -53,6 +53,13 @@ extern "C" {
 
 __attribute__((visibility("hidden"))) hipError_t MPCX_CAT(mpcx_launch_modexp_g, MPCX_GEOM_ID)(
     const mpcx::ModexpArgs* a, uint32_t waves, hipStream_t st) {
+#if MPCX_GEOM_ID == 2
+  if (a->nsq) {  // m = N^2 on N-adic pairs (`waves` counts MxN2's: 16 operands each, as geometry 2's)
+    hipLaunchKernelGGL((mpcx::k_modexp_nsq<MPCX_NSQ_WPE>), dim3((waves + MPCX_NSQ_WG - 1) / MPCX_NSQ_WG),
+                       dim3(64 * MPCX_NSQ_WG), 0, st, *a);
+    return hipGetLastError();
+  }
+#endif
 #if MPCX_GEOM_ID == 2 || MPCX_GEOM_ID == 5
   if (a->mx_img) {  // the reduction on the matrix cores (mpcx_mx.hpp), MX_WG wavefronts per workgroup
     hipLaunchKernelGGL((mpcx::k_modexp_mx<MPCX_GEOM_P(MPCX_GEOM_ID), MPCX_GEOM_K(MPCX_GEOM_ID),

@@ -106,6 +106,10 @@ struct ModexpArgs {
   // matrix cores, MX_WG wavefronts per workgroup. nullptr: k_modexp
   const void* mx_img;
   uint32_t nwaves;      // wavefronts with work (k_modexp_mx: the last workgroup's spare waves exit)
+  // k_modexp_nsq only (m = N^2, N public; nullptr otherwise): MPCX_NSQ_CONST_DIGITS
+  // radix-2^28 digits -- N, then the entry constants a0, b0, a1, b1, MxN2::L each
+  // (MPCX_NSQ_* below); mx_img then holds the Toeplitz tables of N in MxN2's shape
+  const uint32_t* nsq;
 };
 // workgroup: MX_WG wavefronts share the Toeplitz tables and m's digits in LDS
 #ifndef MX_WG
@@ -145,6 +149,25 @@ struct MxShape {
 // k_modexp_mx geometries (mpcx_mx.hpp)
 using MxG2 = MxShape<4, 37, 16>;  // geometry 2: R = 2^4144, 592 radix-2^7 digits
 using MxG5 = MxShape<2, 37, 32>;  // geometry 5: R = 2^2072, 296 radix-2^7 digits
+// k_modexp_nsq: x^e mod N^2 on N-adic pairs (u, v), y R = u + v N (mod N^2) with
+// R = 2^2128: each half is a quad of 19 digits, 16 operands per wave
+using MxN2 = MxShape<4, 19, 16>;
+// a base x < 2^4096 enters as x0 + x1 2^MPCX_NSQ_SPLIT_BITS (74 digits each) through
+// the pairs (a0, b0) = R^2 and (a1, b1) = 2^MPCX_NSQ_SPLIT_BITS R^2 mod N^2
+// (a + b N, a, b < N)
+#define MPCX_NSQ_SPLIT_DIGITS 74
+#define MPCX_NSQ_SPLIT_BITS (28 * MPCX_NSQ_SPLIT_DIGITS)
+#define MPCX_NSQ_CONST_DIGITS (5 * 76)
+// k_modexp_nsq's wavefronts per workgroup (one copy of N's tables in LDS) and per SIMD
+// (register budget): 4 and 2 as k_modexp_mx; 12 and 3 measured in DESIGN.md 5.2h
+#ifndef MPCX_NSQ_WG
+#define MPCX_NSQ_WG 4
+#endif
+#ifndef MPCX_NSQ_WPE
+#define MPCX_NSQ_WPE 2
+#endif
+// digit slots of a window-table entry of k_modexp_nsq (u then v) against K of k_modexp
+#define MPCX_NSQ_TABLE_SLOTS (2 * 19)
 
 
 // Fixed-base tables (mpcx_fixedbase_register): w-bit windows (w chosen per

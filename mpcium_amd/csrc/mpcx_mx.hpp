@@ -128,6 +128,47 @@ __device__ __forceinline__ void mx_product(uint32_t (&A)[K], const uint32_t* bl,
   A[0] += from_prev_lane(ctop);
 }
 
+// Z = U * B + V * A for the rows A (al) and B (bl) in ONE row loop (2 K MADs per row
+// step; k_modexp_nsq's cross term u v' + v u'): Z's low L digits overwrite row B
+// behind the digits the loop has read, the high L digits end in V (<= 2^28 + 2^10).
+// Accumulators: 2 K products < 2^56.001 between two restarts, < 2^61.3 for K = 19.
+template <int P, int K>
+__device__ __forceinline__ void mx_product2(const uint32_t (&U)[K], uint32_t (&V)[K], const uint32_t* al,
+                                            uint32_t* bl, uint32_t* tr, int p) {
+  uint64_t acc[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) acc[k] = 0;
+  uint32_t anext = al[0], bnext = bl[0];
+#pragma nounroll
+  for (int o = 0; o < P; ++o) {
+    const uint32_t* ao = al + o * K;
+    const uint32_t* bo = bl + o * K;
+    uint32_t* to = (p == 0 ? bl : tr) + o * K;
+    static_for<0, K>([&](auto uc) {
+      constexpr int u = decltype(uc)::value;
+      const uint32_t ai = anext, bi = bnext;
+      anext = ao[u + 1];
+      bnext = bo[u + 1];
+      static_for<0, K>([&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        mad64(acc[(k + u) % K], U[k], bi);
+        mad64(acc[(k + u) % K], V[k], ai);
+      });
+      const uint64_t a0 = acc[u];
+      acc[(u + 1) % K] += a0 >> DB;
+      const uint32_t lo = (uint32_t)a0 & M28;
+      to[u] = lo;
+      acc[u] = from_next_lane(p == 0 ? 0u : lo);
+    });
+  }
+  carry_pass64<P, K>(acc);
+  const uint32_t ctop = (uint32_t)(acc[K - 1] >> DB);
+#pragma unroll
+  for (int k = K - 1; k >= 1; --k) V[k] = ((uint32_t)acc[k] & M28) + (uint32_t)(acc[k - 1] >> DB);
+  V[0] = (uint32_t)acc[0] & M28;
+  V[0] += from_prev_lane(ctop);
+}
+
 // lane (n, h) <- lane (n, h - 1) (h = 0: lane (n, 3)); one LDS-crossbar permute
 __device__ __forceinline__ int mx_from_prev_quarter(int v, int lane) {
   return __builtin_amdgcn_ds_bpermute(((lane - 16) & 63) << 2, v);
@@ -155,13 +196,14 @@ __device__ __forceinline__ int mx_hi28(int64_t v) {
 // acc[o - O0] += sum over K blocks kb of F_j (j = o - 4 kb) x bf[kb], for output
 // blocks O0 <= o < O1; Toeplitz block j is read once and used for every kb it
 // pairs with (one block ahead of its MFMAs)
-template <class S, int NJ, int O0, int O1>
+// (ACCUM: on top of what acc holds)
+template <class S, int NJ, int O0, int O1, bool ACCUM = false>
 __device__ __forceinline__ void mx_toeplitz(mx_v4i (&acc)[O1 - O0], const uint8_t* f, const mx_v4i (&bf)[S::KB]) {
   // one ds_read_b128 per block: lane base in a VGPR, block offset an immediate
   auto ld = [&](int j) __attribute__((always_inline)) {
     return *reinterpret_cast<const mx_v4i*>(f + 16 * (S::JMAX - j));
   };
-  static_for<0, O1 - O0>([&](auto oc) { acc[decltype(oc)::value] = mx_v4i{0, 0, 0, 0}; });
+  if constexpr (!ACCUM) static_for<0, O1 - O0>([&](auto oc) { acc[decltype(oc)::value] = mx_v4i{0, 0, 0, 0}; });
   // first and last Toeplitz block with an MFMA in this chunk
   constexpr int JLO = (O0 - 4 * (S::KB - 1)) > 0 ? (O0 - 4 * (S::KB - 1)) : 0;
   constexpr int JHI = (O1 - 1) < (NJ - 1) ? (O1 - 1) : (NJ - 1);
@@ -220,149 +262,51 @@ struct MxProf {
     __builtin_amdgcn_sched_barrier(0);                       \
   } while (0)
 #define MX_PROF_ARG , MxProf* pf
+#define MX_PROF_PASS , pf
 #else
 #define MX_STAMP(i) \
   do {              \
   } while (0)
 #define MX_PROF_ARG
+#define MX_PROF_PASS
 #endif
-template <class S, bool SQR, bool B2IN>
-__device__ __forceinline__ void montmul_mx(uint32_t (&A)[S::K], uint32_t* rows, const uint32_t* md,
-                                           const MxConsts& c, int lane MX_PROF_ARG) {
-  constexpr int P = S::P, K = S::K, L = S::L, ROW = S::ROW, KB = S::KB;
-  const int g = lane / P, p = lane % P;    // block layout
-  const int n = lane & 15, h = lane >> 4;  // MFMA layout
-  uint32_t* rg = rows + g * ROW;
-  // ---- T = A B on the VALU: low digits -> the row (behind the multiplier digits
-  // the loop has read), high digits -> A
 #ifndef MPCX_MX_TIMING
 #define MPCX_MX_TIMING 0  // microbench builds only: 1 = product loop alone, 2 = reduction alone
 #endif
-  // The wave's issue priority by phase of the Montgomery product (s_setprio; the
-  // two waves of a SIMD are mostly in different phases). The levels fall along
-  // the product, so whenever the two waves are in different phases the one that
-  // is earlier in its product issues first and the other fills the slots it
-  // leaves: config 2 at 123.3 ms, the fastest of the orders tried
-  // (profiles/r06/prioab2..5).
-  constexpr int PRIO_PRODUCT = 3;  // product loop
-  constexpr int PRIO_FRAG = 2;     // fragment build
-  constexpr int PRIO_Q = 1;        // q products
-  constexpr int PRIO_QM = 0;       // q m products
-  constexpr int PRIO_CARRY = 0;    // carry passes
-  MX_STAMP(0);
-  __builtin_amdgcn_s_setprio(PRIO_PRODUCT);
-  if constexpr (MPCX_MX_TIMING != 2) mx_product<P, K, SQR, B2IN>(A, rg, rg, rows + S::TRASH_OFF + lane, p);
-  __builtin_amdgcn_s_setprio(PRIO_FRAG);
-  MX_STAMP(1);
-  if constexpr (MPCX_MX_TIMING == 1) return;
-  wave_lds_fence();
-  // ---- T's low half as B fragments (radix-2^7 bytes), every half of the wave
-  mx_v4i bf[S::HALVES][KB];
-  int ttop[S::HALVES];  // T's digit L - 1: the top 4 positions of the carry estimate
-  static_for<0, S::HALVES>([&](auto sc) {
-    constexpr int s = decltype(sc)::value;
-    const uint32_t* rn = rows + (16 * s + n) * ROW;
-    static_for<0, KB>([&](auto kc) {
-      constexpr int kb = decltype(kc)::value;
-      mx_v4i v = {0, 0, 0, 0};
-      if (16 * kb + 4 * h < L) v = *reinterpret_cast<const mx_v4i*>(rn + 16 * kb + 4 * h);
-      if constexpr (16 * kb + 15 >= L) {  // the digits past L in the last K block
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          if (16 * kb + 4 * h + i >= L) v[i] = 0;
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = (int)mx_spread7((uint32_t)v[i]);
-      bf[s][kb] = v;
-    });
-    ttop[s] = (int)rn[L - 1];
-  });
-  wave_lds_fence();
-  MX_STAMP(2);
-  // ---- the row <- T's high digits + m (block layout)
-#pragma unroll
-  for (int k = 0; k < K; ++k) rg[p * K + k] = A[k] + md[p * K + k];
-  __builtin_amdgcn_s_setprio(PRIO_Q);
-  static_for<0, S::HALVES>([&](auto sc) {
-    constexpr int s = decltype(sc)::value;
-    uint32_t* rn = rows + (16 * s + n) * ROW;
-    if constexpr (s > 0) __builtin_amdgcn_s_setprio(PRIO_Q);  // the first half left it at PRIO_QM
-    // ---- q column sums (o = j + 4 kb; chunks of output blocks bound the live
-    // accumulators), balanced radix-2^28 digits with one carry step, as bytes;
-    // every 4 blocks transposed in registers into one B fragment of phase 2
-    mx_v4i qf[KB];
-    {
-      int xprev = 0;
-      uint32_t X[4] = {0u, 0u, 0u, 0u};
-      auto norm = [&](const mx_v4i& cs, int o) __attribute__((always_inline)) -> uint32_t {
-        const int64_t v = mx_sum64(cs, 1 << 27);
-        const int lo = ((int)(uint32_t)v & (int)M28) - (1 << 27);
-        const int hi = mx_hi28(v);
-        const int x = mx_from_prev_quarter(hi, lane);
-        int e = lo + (h == 0 ? xprev : x);
-        xprev = x;
-        if (4 * o + 3 >= L && 4 * o + h >= L) e = 0;  // digits past L: q is mod R
-        return mx_spread7((uint32_t)e);
-      };
-      auto norm_block = [&](const mx_v4i& cs, auto oc) __attribute__((always_inline)) {
-        constexpr int o = decltype(oc)::value;
-        X[o & 3] = norm(cs, o);
-        if constexpr ((o & 3) == 3) {
-          qf[o >> 2] = mx_transpose4(X[0], X[1], X[2], X[3]);
-        } else if constexpr (o == S::O1 - 1) {
-          qf[o >> 2] = mx_transpose4(X[0], (o & 3) >= 1 ? X[1] : 0u, (o & 3) >= 2 ? X[2] : 0u, 0u);
-        }
-      };
-      constexpr int NC = (S::O1 + S::CS1 - 1) / S::CS1;
-      static_for<0, NC>([&](auto cc) {
-        constexpr int O0 = S::CS1 * decltype(cc)::value;
-        constexpr int O1 = O0 + S::CS1 < S::O1 ? O0 + S::CS1 : S::O1;
-        mx_v4i acc[O1 - O0];
-        mx_toeplitz<S, S::NJ1, O0, O1>(acc, c.t1, bf[s]);
-        static_for<0, O1 - O0>([&](auto oc) {
-          norm_block(acc[decltype(oc)::value], std::integral_constant<int, O0 + decltype(oc)::value>{});
-        });
-        __builtin_amdgcn_sched_barrier(0);  // one chunk's accumulators live at a time
-      });
-    }
-    MX_STAMP(3);
-    __builtin_amdgcn_s_setprio(PRIO_QM);
-    // ---- q m column sums for blocks O2LO.. : the lane whose 4 positions are the
-    // low half's top (N7 - 4 .. N7 - 1) gives the carry out of the low half, the
-    // lanes at positions N7 + 4d the digits d of U + m, adding T's high digit + m
-    // from the row; the carry chain runs through the quarters as in q
-    {
-      int xprev = 0;
-      auto emit = [&](const mx_v4i& cs, int o) __attribute__((always_inline)) {
-        const int pos = 16 * o + 4 * h;
-        const bool carry_lane = pos == S::N7 - 4;
-        const int d = (pos - S::N7) >> 2;  // U's digit (< 0: the low half)
-        const int dc = d < 0 ? 0 : d;
-        const int add = carry_lane ? ttop[s] + (1 << 27) : (int)rn[dc];
-        const int64_t v = mx_sum64(cs, add);
-        const int hi = mx_hi28(v);        // on the carry lane: round(low half / R)
-        const int top = (int)(uint32_t)v;  // the sum mod 2^32
-        const int dig = top & (int)M28;    // the sum's bits 0..27
-        const int x = mx_from_prev_quarter(hi, lane);
-        const int cin = h == 0 ? xprev : x;
-        xprev = x;
-        // the top digit keeps its carry (the value is < 2m < 2^(28 L - 47))
-        const int u = d == L - 1 ? top + cin : dig + cin;
-        if (d >= 0) rn[dc] = (uint32_t)u;
-      };
-      constexpr int NC = (S::O2HI - S::O2LO + S::CS2 - 1) / S::CS2;
-      static_for<0, NC>([&](auto cc) {
-        constexpr int O0 = S::O2LO + S::CS2 * decltype(cc)::value;
-        constexpr int O1 = O0 + S::CS2 < S::O2HI ? O0 + S::CS2 : S::O2HI;
-        mx_v4i acc[O1 - O0];
-        mx_toeplitz<S, S::NJ2, O0, O1>(acc, c.t2, qf);
-        static_for<0, O1 - O0>([&](auto oc) { emit(acc[decltype(oc)::value], O0 + decltype(oc)::value); });
-        __builtin_amdgcn_sched_barrier(0);
-      });
-    }
-  });
-  __builtin_amdgcn_s_setprio(PRIO_CARRY);
-  MX_STAMP(4);
+
+// The wave's issue priority by phase of the Montgomery product (s_setprio; the
+// two waves of a SIMD are mostly in different phases). The levels fall along
+// the product, so whenever the two waves are in different phases the one that
+// is earlier in its product issues first and the other fills the slots it
+// leaves: config 2 at 123.3 ms, the fastest of the orders tried
+// (profiles/r06/prioab2..5).
+constexpr int PRIO_PRODUCT = 3;  // product loop
+constexpr int PRIO_FRAG = 2;     // fragment build
+constexpr int PRIO_Q = 1;        // q products
+constexpr int PRIO_QM = 0;       // q m products
+constexpr int PRIO_CARRY = 0;    // carry passes
+
+// The quotient of one reduction, handed to a second one (k_modexp_nsq, below): its
+// bytes NEGATED, as B fragments, and its top radix-2^28 digit L - 1 (in the lane
+// that estimates the carry out of the low half)
+template <class S>
+struct MxQ {
+  mx_v4i f[S::KB];
+  int top;
+};
+
+// every byte b of x (|b| <= 127) -> -b, no borrow between bytes
+__device__ __forceinline__ int mx_neg_bytes(int x) {
+  const uint32_t b = (uint32_t)x, H = 0x80808080u;
+  return (int)((H - (b & ~H)) ^ (~b & H));
+}
+
+// The end of a reduction: U + m from the row back to the block layout, and signed
+// carry passes until every digit is >= 0 (k_modexp_nsq reads both halves back after
+// the second reduction, so neither is live during the other's)
+template <class S>
+__device__ __forceinline__ void mx_readback(uint32_t (&A)[S::K], const uint32_t* rg, int p MX_PROF_ARG) {
+  constexpr int P = S::P, K = S::K, L = S::L;
   wave_lds_fence();
   // ---- back to the block layout; signed carry passes until every digit is >= 0
 #pragma unroll
@@ -392,6 +336,191 @@ __device__ __forceinline__ void montmul_mx(uint32_t (&A)[S::K], uint32_t* rows, 
     if (!__any(neg)) break;
   }
   MX_STAMP(6);
+}
+
+// The reduction of montmul_mx: T's low digits in the rows, its high digits in A;
+// A <- (T + q m) / R + m, q balanced. MODE 0: that alone. The pair of reductions of
+// a product mod m^2 in m-adic form (mpcx_device.hpp, k_modexp_nsq):
+// MODE 1 also hands out its q; MODE 2 reduces T - q1 - R for the q1 handed in:
+//  * its q is ((T mod R) - q1) m'' mod R: a second Toeplitz pass over q1's negated
+//    bytes into the same column sums (|sum| < 2 * 4 L * 127^2 < 2^24 for L = 76);
+//  * the carry out of the low half T_low - q1 + (q m)_low takes q1's top digit too
+//    (q1's lower digits weigh < 2^-28 of a carry unit);
+//  * the high half adds m - 1: - R is one unit there, and with |q|, |q1| <= R/2
+//    (1 + 2^-10) the result (T - q1 + q m) / R - 1 + m stays within m/2 (1 - 2^-10) - 2
+//    and 3m/2 (1 + 2^-10) + 2 + T/R.
+template <class S, int MODE>
+__device__ __forceinline__ void mx_reduce(uint32_t (&A)[S::K], uint32_t* rows, const uint32_t* md,
+                                          const MxConsts& c, int lane, MxQ<S>& q1 MX_PROF_ARG) {
+  static_assert(MODE == 0 || S::HALVES == 1, "the pair of reductions serves 16 operands per wave");
+  constexpr int P = S::P, K = S::K, L = S::L, ROW = S::ROW, KB = S::KB;
+  const int g = lane / P, p = lane % P;    // block layout
+  const int n = lane & 15, h = lane >> 4;  // MFMA layout
+  uint32_t* rg = rows + g * ROW;
+  __builtin_amdgcn_s_setprio(PRIO_FRAG);
+  MX_STAMP(1);
+  if constexpr (MPCX_MX_TIMING == 1) return;
+  wave_lds_fence();
+  // ---- T's low half as B fragments (radix-2^7 bytes), every half of the wave
+  mx_v4i bf[S::HALVES][KB];
+  int ttop[S::HALVES];  // T's digit L - 1: the top 4 positions of the carry estimate
+  static_for<0, S::HALVES>([&](auto sc) {
+    constexpr int s = decltype(sc)::value;
+    const uint32_t* rn = rows + (16 * s + n) * ROW;
+    static_for<0, KB>([&](auto kc) {
+      constexpr int kb = decltype(kc)::value;
+      mx_v4i v = {0, 0, 0, 0};
+      if (16 * kb + 4 * h < L) v = *reinterpret_cast<const mx_v4i*>(rn + 16 * kb + 4 * h);
+      if constexpr (16 * kb + 15 >= L) {  // the digits past L in the last K block
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (16 * kb + 4 * h + i >= L) v[i] = 0;
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) v[i] = (int)mx_spread7((uint32_t)v[i]);
+      bf[s][kb] = v;
+    });
+    ttop[s] = (int)rn[L - 1];
+  });
+  wave_lds_fence();
+  MX_STAMP(2);
+  // ---- the row <- T's high digits + m (block layout)
+#pragma unroll
+  for (int k = 0; k < K; ++k) rg[p * K + k] = A[k] + md[p * K + k] - (MODE == 2 && k == 0 && p == 0 ? 1u : 0u);
+  __builtin_amdgcn_s_setprio(PRIO_Q);
+  static_for<0, S::HALVES>([&](auto sc) {
+    constexpr int s = decltype(sc)::value;
+    uint32_t* rn = rows + (16 * s + n) * ROW;
+    if constexpr (s > 0) __builtin_amdgcn_s_setprio(PRIO_Q);  // the first half left it at PRIO_QM
+    // ---- q column sums (o = j + 4 kb; chunks of output blocks bound the live
+    // accumulators), balanced radix-2^28 digits with one carry step, as bytes;
+    // every 4 blocks transposed in registers into one B fragment of phase 2
+    mx_v4i qf_own[KB];
+    mx_v4i(&qf)[KB] = MODE == 1 ? q1.f : qf_own;
+    {
+      int xprev = 0;
+      uint32_t X[4] = {0u, 0u, 0u, 0u};
+      auto norm = [&](const mx_v4i& cs, int o) __attribute__((always_inline)) -> uint32_t {
+        const int64_t v = mx_sum64(cs, 1 << 27);
+        const int lo = ((int)(uint32_t)v & (int)M28) - (1 << 27);
+        const int hi = mx_hi28(v);
+        const int x = mx_from_prev_quarter(hi, lane);
+        int e = lo + (h == 0 ? xprev : x);
+        xprev = x;
+        if (4 * o + 3 >= L && 4 * o + h >= L) e = 0;  // digits past L: q is mod R
+        if (MODE == 1 && o == (L - 1) / 4) q1.top = e;  // lane h = (L - 1) % 4: digit L - 1
+        return mx_spread7((uint32_t)e);
+      };
+      auto norm_block = [&](const mx_v4i& cs, auto oc) __attribute__((always_inline)) {
+        constexpr int o = decltype(oc)::value;
+        X[o & 3] = norm(cs, o);
+        if constexpr ((o & 3) == 3) {
+          qf[o >> 2] = mx_transpose4(X[0], X[1], X[2], X[3]);
+        } else if constexpr (o == S::O1 - 1) {
+          qf[o >> 2] = mx_transpose4(X[0], (o & 3) >= 1 ? X[1] : 0u, (o & 3) >= 2 ? X[2] : 0u, 0u);
+        }
+      };
+      constexpr int NC = (S::O1 + S::CS1 - 1) / S::CS1;
+      static_for<0, NC>([&](auto cc) {
+        constexpr int O0 = S::CS1 * decltype(cc)::value;
+        constexpr int O1 = O0 + S::CS1 < S::O1 ? O0 + S::CS1 : S::O1;
+        mx_v4i acc[O1 - O0];
+        mx_toeplitz<S, S::NJ1, O0, O1>(acc, c.t1, bf[s]);
+        if constexpr (MODE == 2) mx_toeplitz<S, S::NJ1, O0, O1, true>(acc, c.t1, q1.f);
+        static_for<0, O1 - O0>([&](auto oc) {
+          norm_block(acc[decltype(oc)::value], std::integral_constant<int, O0 + decltype(oc)::value>{});
+        });
+        __builtin_amdgcn_sched_barrier(0);  // one chunk's accumulators live at a time
+      });
+    }
+    MX_STAMP(3);
+    __builtin_amdgcn_s_setprio(PRIO_QM);
+    // ---- q m column sums for blocks O2LO.. : the lane whose 4 positions are the
+    // low half's top (N7 - 4 .. N7 - 1) gives the carry out of the low half, the
+    // lanes at positions N7 + 4d the digits d of U + m, adding T's high digit + m
+    // from the row; the carry chain runs through the quarters as in q
+    {
+      int xprev = 0;
+      auto emit = [&](const mx_v4i& cs, int o) __attribute__((always_inline)) {
+        const int pos = 16 * o + 4 * h;
+        const bool carry_lane = pos == S::N7 - 4;
+        const int d = (pos - S::N7) >> 2;  // U's digit (< 0: the low half)
+        const int dc = d < 0 ? 0 : d;
+        const int add = carry_lane ? ttop[s] + (1 << 27) - (MODE == 2 ? q1.top : 0) : (int)rn[dc];
+        const int64_t v = mx_sum64(cs, add);
+        const int hi = mx_hi28(v);        // on the carry lane: round(low half / R)
+        const int top = (int)(uint32_t)v;  // the sum mod 2^32
+        const int dig = top & (int)M28;    // the sum's bits 0..27
+        const int x = mx_from_prev_quarter(hi, lane);
+        const int cin = h == 0 ? xprev : x;
+        xprev = x;
+        // the top digit keeps its carry (the value is < 2m < 2^(28 L - 47))
+        const int u = d == L - 1 ? top + cin : dig + cin;
+        if (d >= 0) rn[dc] = (uint32_t)u;
+      };
+      constexpr int NC = (S::O2HI - S::O2LO + S::CS2 - 1) / S::CS2;
+      static_for<0, NC>([&](auto cc) {
+        constexpr int O0 = S::O2LO + S::CS2 * decltype(cc)::value;
+        constexpr int O1 = O0 + S::CS2 < S::O2HI ? O0 + S::CS2 : S::O2HI;
+        mx_v4i acc[O1 - O0];
+        mx_toeplitz<S, S::NJ2, O0, O1>(acc, c.t2, qf);
+        static_for<0, O1 - O0>([&](auto oc) { emit(acc[decltype(oc)::value], O0 + decltype(oc)::value); });
+        __builtin_amdgcn_sched_barrier(0);
+      });
+    }
+    if constexpr (MODE == 1) {  // the second reduction subtracts this q
+#pragma unroll
+      for (int kb = 0; kb < KB; ++kb)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) q1.f[kb][i] = mx_neg_bytes(q1.f[kb][i]);
+    }
+  });
+  __builtin_amdgcn_s_setprio(PRIO_CARRY);
+  MX_STAMP(4);
+  if constexpr (MODE == 0) mx_readback<S>(A, rg, p MX_PROF_PASS);
+}
+
+template <class S, bool SQR, bool B2IN>
+__device__ __forceinline__ void montmul_mx(uint32_t (&A)[S::K], uint32_t* rows, const uint32_t* md,
+                                           const MxConsts& c, int lane MX_PROF_ARG) {
+  uint32_t* rg = rows + (lane / S::P) * S::ROW;
+  // ---- T = A B on the VALU: low digits -> the row (behind the multiplier digits
+  // the loop has read), high digits -> A
+  MX_STAMP(0);
+  __builtin_amdgcn_s_setprio(PRIO_PRODUCT);
+  if constexpr (MPCX_MX_TIMING != 2)
+    mx_product<S::P, S::K, SQR, B2IN>(A, rg, rg, rows + S::TRASH_OFF + lane, lane % S::P);
+  MxQ<S> q;  // unused
+  mx_reduce<S, 0>(A, rows, md, c, lane, q MX_PROF_PASS);
+}
+
+// (u, v) <- (u, v) x (a, b) mod m^2 in m-adic Montgomery form (k_modexp_nsq,
+// mpcx_device.hpp): u <- montmul_mx(u, a) = (u a + q m) / R + m and
+// v <- (u b + v a - q - R) / R mod m, the second reduction taking the first one's q
+// (u a = R u' - (q + R) m, so the pair stands for (u + v m)(a + b m) / R mod m^2; the
+// v b m^2 term is never formed). ra / rb: the wave's row sets with a and b
+// (operand g's rows at g * ROW), both scratch as montmul_mx's row.
+// SQR: (a, b) = (u, v) with 2u in BOTH rows: u^2 on row a and 2 u v = v x row b.
+template <class S, bool SQR>
+__device__ __forceinline__ void pairmul_mx(uint32_t (&U)[S::K], uint32_t (&V)[S::K], uint32_t* ra, uint32_t* rb,
+                                           uint32_t* tr, const uint32_t* md, const MxConsts& c, int lane) {
+  constexpr int P = S::P, K = S::K;
+  const int g = lane / P, p = lane % P;
+  uint32_t* ga = ra + g * S::ROW;
+  uint32_t* gb = rb + g * S::ROW;
+  __builtin_amdgcn_s_setprio(PRIO_PRODUCT);
+  if constexpr (SQR) {
+    mx_product<P, K, false, false>(V, gb, gb, tr, p);
+    mx_product<P, K, true, true>(U, ga, ga, tr, p);
+  } else {
+    mx_product2<P, K>(U, V, ga, gb, tr, p);
+    mx_product<P, K, false, false>(U, ga, ga, tr, p);
+  }
+  MxQ<S> q;
+  mx_reduce<S, 1>(U, ra, md, c, lane, q);
+  mx_reduce<S, 2>(V, rb, md, c, lane, q);
+  mx_readback<S>(U, ga, p);
+  mx_readback<S>(V, gb, p);
 }
 
 }  // namespace mpcx

@@ -40,6 +40,7 @@ SIGNATURES = [
     ("mpcx_modulus_info", ctypes.c_int, [_vp, _u32p, _u32p]),
     ("mpcx_modulus_geometry", ctypes.c_int, [_vp, _u32p, _u32p, _u32p, _u32p]),
     ("mpcx_mx_tables", ctypes.c_int, [_u32p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t]),
+    ("mpcx_nsq_consts", ctypes.c_int, [_u32p, ctypes.c_uint32, _u32p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_int)]),
     ("mpcx_modexp_batch", ctypes.c_int, [_vp, ctypes.c_uint32, _vp, ctypes.c_uint32, _vp, ctypes.c_uint32,
                                          ctypes.c_int, _vp, ctypes.c_uint32]),
     ("mpcx_modexp_batch_device", ctypes.c_int, [_vp, ctypes.c_uint32, _vp, ctypes.c_uint32, _vp, ctypes.c_uint32,
@@ -176,7 +177,7 @@ def copy_stats() -> dict:
     return {"direct_bytes": v[0].value, "bounced_bytes": v[1].value, "bounce_allocs": v[2].value}
 
 
-MX_TABLE_BYTES = {148: 2 * 16 * 720, 74: 2 * 16 * 432}
+MX_TABLE_BYTES = {148: 2 * 16 * 720, 76: 2 * 16 * 432, 74: 2 * 16 * 432}
 
 
 def mx_tables(m: int, L: int = 148) -> bytes:
@@ -187,6 +188,22 @@ def mx_tables(m: int, L: int = 148) -> bytes:
     out = ctypes.create_string_buffer(max(n, 1))
     _check(lib().mpcx_mx_tables(w.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), 128, L, out, n))
     return out.raw
+
+
+def nsq_consts(m: int):
+    """mpcx_nsq_consts: None when m is not a perfect square k_modexp_nsq serves, else
+    (N, (a0, b0), (a1, b1), tables): the entry constants as integers and the bytes of
+    mpcx_mx_tables(N, 76) (host-only, no device needed)."""
+    w = int_to_words(m, 128)
+    n = 5 * 76 + MX_TABLE_BYTES[76] // 4
+    out = np.zeros(n, dtype="<u4")
+    sq = ctypes.c_int(0)
+    u32p = ctypes.POINTER(ctypes.c_uint32)
+    _check(lib().mpcx_nsq_consts(w.ctypes.data_as(u32p), 128, out.ctypes.data_as(u32p), n, ctypes.byref(sq)))
+    if not sq.value:
+        return None
+    v = [sum(int(d) << (28 * i) for i, d in enumerate(out[76 * j:76 * j + 76])) for j in range(5)]
+    return v[0], (v[1], v[2]), (v[3], v[4]), out[380:].tobytes()
 
 
 def select_device(index: int):
