@@ -468,6 +468,30 @@ int mpcx_mx_tables(const uint32_t* m_words, uint32_t m_len, uint32_t L, uint8_t*
  * an N of 1025..2048 bits. Host-only (no device needed); for tests and tools. */
 int mpcx_nsq_consts(const uint32_t* m_words, uint32_t m_len, uint32_t* out, size_t cap_words, int* is_square);
 
+/* One secp256k1 field or point operation of k_ec_combine's device code
+ * (mpcium_amd/csrc/mpcx_ec_fe.hpp) per item, one GPU thread each, on the
+ * calling thread's selected device; for tests and tools. a, b, out: count x 24
+ * little-endian words per item -- a Jacobian point X, Y, Z (Z == 0: infinity),
+ * or a field element in the first 8 words:
+ *   ADD, SUB, MUL   out[0..8) = a[0..8) op b[0..8) mod p
+ *   SQR, INV        out[0..8) = a^2, a^(p-2) mod p (b is not used)
+ *   JAC_DBL         out = 2 a (b is not used)
+ *   JAC_ADD         out = a + b, both Jacobian
+ *   JAC_MADD        out = a + the affine point (b.X, b.Y) (b.Z is not used)
+ * Field results leave out[8..24) zero. Point results are Jacobian, not
+ * normalised. MPCX_EINVAL for an unknown op, a null buffer, or any of the six
+ * 8-word input values of an item >= p (whether the op reads it or not): the
+ * device functions take values below p only. */
+#define MPCX_EC_OP_ADD 0
+#define MPCX_EC_OP_SUB 1
+#define MPCX_EC_OP_MUL 2
+#define MPCX_EC_OP_SQR 3
+#define MPCX_EC_OP_INV 4
+#define MPCX_EC_OP_JAC_DBL 5
+#define MPCX_EC_OP_JAC_ADD 6
+#define MPCX_EC_OP_JAC_MADD 7
+int mpcx_ec_probe(uint32_t op, uint32_t count, const uint32_t* a, const uint32_t* b, uint32_t* out);
+
 /* Kernel-class geometry of a modulus (for benchmarks and roofline math):
  * digits L (radix 2^28), lanes per operand P, digits per lane K, operands per
  * 64-lane wavefront G. */

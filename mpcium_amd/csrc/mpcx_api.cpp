@@ -65,6 +65,8 @@ hipError_t mpcx_launch_sieve(const mpcx::SieveArgs* a, hipStream_t st);
 hipError_t mpcx_launch_selftest(uint32_t* d_out, hipStream_t st);
 hipError_t mpcx_launch_ec_combine(const uint32_t* sc, const uint32_t* pts, uint32_t* out, const uint32_t* gtab,
                                   uint32_t* ws, uint32_t count, hipStream_t st);
+hipError_t mpcx_launch_ec_probe(uint32_t op, const uint32_t* a, const uint32_t* b, uint32_t* out, uint32_t count,
+                                hipStream_t st);
 }
 
 namespace {
@@ -2499,6 +2501,41 @@ int mpcx_ec_combine_batch(uint32_t count, const uint32_t* scalars, const uint32_
   return run_sliced(count, g_split_min, [&](int di, uint32_t first, uint32_t n) {
     return ec_range(di, n, scalars + (size_t)first * 24u, points + (size_t)first * 32u, out + (size_t)first * 16u);
   });
+}
+
+// One field or point operation of mpcx_ec_fe.hpp per item (k_ec_probe), on the
+// thread's selected device; for tests and tools.
+int mpcx_ec_probe(uint32_t op, uint32_t count, const uint32_t* a, const uint32_t* b, uint32_t* out) {
+  if (op > MPCX_EC_OP_JAC_MADD) return fail(MPCX_EINVAL, "unknown secp256k1 probe op %u", op);
+  if (!a || !b || !out) return fail(MPCX_EINVAL, "null buffer");
+  if (count == 0) return MPCX_OK;
+  // every input value < p = 2^256 - 2^32 - 977: limbs 2..7 all ones and (limb 1, limb 0) >= (p1, p0) is >= p
+  for (int s = 0; s < 2; ++s) {
+    const uint32_t* in = s ? b : a;
+    for (size_t e = 0; e < (size_t)count * 3u; ++e) {
+      const uint32_t* v = in + e * 8u;
+      uint32_t hi = 0xFFFFFFFFu;
+      for (int i = 2; i < 8; ++i) hi &= v[i];
+      if (hi == 0xFFFFFFFFu && (v[1] == 0xFFFFFFFFu || (v[1] == 0xFFFFFFFEu && v[0] >= 0xFFFFFC2Fu)))
+        return fail(MPCX_EINVAL, "item %zu: value %zu of input %c is >= p", e / 3u, e % 3u, s ? 'b' : 'a');
+    }
+  }
+  Device* dev = nullptr;
+  int rc;
+  if ((rc = selected(&dev))) return rc;
+  std::unique_lock<std::mutex> lk;
+  Lane& l = acquire_lane(*dev, lk);
+  LaneDrain drain(l);
+  if ((rc = lane_stream(l))) return rc;
+  const size_t nb = (size_t)count * 24u * 4u;
+  if ((rc = ensure_buffer(l.stage[0], nb)) || (rc = ensure_buffer(l.stage[1], nb)) ||
+      (rc = ensure_buffer(l.stage[2], nb)))
+    return rc;
+  if ((rc = h2d(l, l.stage[0].ptr, a, nb)) || (rc = h2d(l, l.stage[1].ptr, b, nb))) return rc;
+  const hipError_t e = mpcx_launch_ec_probe(op, (const uint32_t*)l.stage[0].ptr, (const uint32_t*)l.stage[1].ptr,
+                                            (uint32_t*)l.stage[2].ptr, count, l.st);
+  if (e != hipSuccess) return hip_fail(e, "launch k_ec_probe");
+  return d2h_sync(out, l.stage[2].ptr, nb, l);
 }
 
 int mpcx_fermat2_batch(uint32_t count, const uint32_t* p, uint32_t p_words, uint8_t* ok) {

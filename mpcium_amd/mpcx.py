@@ -59,6 +59,7 @@ SIGNATURES = [
                                          ctypes.c_uint32]),
     ("mpcx_fermat2_batch", ctypes.c_int, [ctypes.c_uint32, _vp, ctypes.c_uint32, _vp]),
     ("mpcx_ec_combine_batch", ctypes.c_int, [ctypes.c_uint32, _vp, _vp, _vp]),
+    ("mpcx_ec_probe", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp]),
     ("mpcx_modexp_multi_batch", ctypes.c_int, [ctypes.c_uint32, _vp]),
     ("mpcx_mr_batch", ctypes.c_int, [ctypes.c_uint32, _vp, ctypes.c_uint32, _vp, _vp]),
     ("mpcx_fixedbase_register", ctypes.c_int, [_vp, _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_vp)]),
@@ -530,6 +531,40 @@ def ec_combine_batch(items) -> list:
     for v in words_to_ints(out):
         res.append(None if v == 0 else (v & mask, v >> 256))
     return res
+
+
+EC_OPS = {"add": 0, "sub": 1, "mul": 2, "sqr": 3, "inv": 4, "jac_dbl": 5, "jac_add": 6, "jac_madd": 7}
+
+
+def ec_probe(op: Union[str, int], a: Sequence, b: Optional[Sequence] = None) -> list:
+    """mpcx_ec_probe (for tests and tools): one field or point operation of the
+    secp256k1 kernel per item. An item of a / b is a field element (int) or a
+    point as a tuple of up to three ints (X, Y, Z; missing ones are 0); b
+    defaults to zeros. Field ops return ints, point ops (X, Y, Z) tuples."""
+    code = EC_OPS[op] if isinstance(op, str) else int(op)
+    n = len(a)
+    if b is None:
+        b = [0] * n
+    if len(b) != n:
+        raise ValueError("length mismatch")
+
+    def pack(items):
+        vals = []
+        for it in items:
+            t = tuple(it) if isinstance(it, (tuple, list)) else (it,)
+            if len(t) > 3 or any(v < 0 or v >> 256 for v in t):
+                raise ValueError("a probe item is up to three values in [0, 2^256)")
+            vals.append(sum(int(v) << (256 * i) for i, v in enumerate(t)))
+        return ints_to_words(vals, 24) if n else np.zeros((1, 24), dtype="<u4")
+
+    A, B = pack(a), pack(b)
+    out = np.zeros((max(n, 1), 24), dtype="<u4")
+    _check(lib().mpcx_ec_probe(code, n, A.ctypes.data, B.ctypes.data, out.ctypes.data))
+    mask = (1 << 256) - 1
+    res = words_to_ints(out[:n])
+    if code <= EC_OPS["inv"]:
+        return [v & mask for v in res]
+    return [(v & mask, (v >> 256) & mask, v >> 512) for v in res]
 
 
 def fermat2_batch(cands: Sequence[int]) -> List[bool]:
