@@ -253,6 +253,25 @@ int mpcx_modexp_multi_batch(uint32_t n_groups, const mpcx_modexp_group_t* groups
  * crypto.NewECPoint does); out: count x 16 words (x, y; all zero = infinity). */
 int mpcx_ec_combine_batch(uint32_t count, const uint32_t* scalars, const uint32_t* points, uint32_t* out);
 
+#define MPCX_EC_MSM_MAX_POINTS 16
+/* out_i = a_i G + sum_{k < n_points} b_ik P_ik  (up:crypto/vss feldman_vss.go
+ * (*Share).Verify and Create; keygen round 3 / resharing BigXj; sums of points)
+ * for count independent items, one GPU thread each (k_ec_msm: Straus, 4-bit
+ * windows, starting at the highest window any item of a wavefront uses).
+ * 1 <= n_points <= MPCX_EC_MSM_MAX_POINTS, the same for every item: a shorter
+ * item is padded with zero scalars or all-zero points, and a longer sum is
+ * chained by feeding an output back as a point. Scalars and points are as in
+ * mpcx_ec_combine_batch: 8 little-endian words per scalar, any 256-bit value;
+ * a term whose scalar is zero or whose point is all-zero is dropped; other
+ * points must be on the curve (the caller checks). The argument checks come
+ * before any device is touched: n_points out of range or a null scalars,
+ * points or out is MPCX_EINVAL; count == 0 is MPCX_OK. */
+int mpcx_ec_msm_batch(uint32_t count, uint32_t n_points,
+                      const uint32_t* a,        /* count x 8 words, or NULL: no G term */
+                      const uint32_t* scalars,  /* count x n_points x 8 words */
+                      const uint32_t* points,   /* count x n_points x 16 words (x, y); all-zero = infinity */
+                      uint32_t* out);           /* count x 16 words; all-zero = infinity */
+
 /* Miller-Rabin: ok[i] = n_i is a strong probable prime to base bases[i]
  * (5 <= n_i < 2^1024 odd, bases[i] < 2^(32*n_words); a base that is 0 mod
  * n_i reports "composite"). Each candidate is its own modulus. Serves
@@ -442,13 +461,17 @@ int mpcx_sync(void* stream);
  *                run concurrently on a one-GPU box.
  *   "kernel_stats" 0 (default) / 1: time every batch-entry-point launch
  *                with an event pair for mpcx_kernel_stats.
+ *   "ec_msm_ws_mb" 1..4096 (default 512): cap, in MB, on the per-thread table
+ *                workspace of one k_ec_msm launch (92,160 B per 64-item block
+ *                and point); mpcx_ec_msm_batch cuts a device's slice into
+ *                consecutive launches under it, never below one block.
  * Environment, read at mpcx_init / mpcx_init_devices: MPCX_LANES (1..8,
  * default 6: execution lanes per device), MPCX_GEOM_POLICY, MPCX_NARROW_ROUNDS,
  * MPCX_FB_WINDOW, MPCX_MX, MPCX_NSQ, MPCX_MX_STEP, MPCX_GEOM_TPUT. */
 int mpcx_set_option(const char* key, int value);
 /* Current value of "mx", "nsq", "mx_min", "mx_seg_min", "mx_step", "geom_tput",
- * "geom_policy", "sched_width", "fixed_window", "fb_split" or "lanes"
- * (benchmarks record which kernel path ran). */
+ * "geom_policy", "sched_width", "fixed_window", "fb_split", "lanes" or
+ * "ec_msm_ws_mb" (benchmarks record which kernel path ran). */
 int mpcx_get_option(const char* key, int* value);
 
 /* The constant tables of k_modexp_mx (the 4096- and 2048-bit main geometries

@@ -22,6 +22,11 @@
  *   mpcxh_mta_*_batch            up:crypto/mta/{share_protocol,range_proof,proofs}.go
  *                                (AliceInit, BobMid[WC], AliceEnd[WC], the
  *                                 range / Bob proofs and their Verify)
+ *   mpcxh_vss_create_batch       up:crypto/vss/feldman_vss.go Create
+ *   mpcxh_vss_verify_batch       up:crypto/vss/feldman_vss.go (*Share).Verify
+ *   mpcxh_vss_public_shares_batch  up:ecdsa/keygen/round_3.go, up:ecdsa/resharing/round_4_new_step_2.go
+ *                                (Vc = sum of the parties' Vs, BigXj = sum_k id_j^k Vc_k)
+ *   mpcxh_vss_reconstruct_batch  up:crypto/vss/feldman_vss.go (Shares).ReConstruct
  */
 #ifndef MPCX_HOST_H_
 #define MPCX_HOST_H_
@@ -228,6 +233,46 @@ int mpcxh_fac_prove_batch(uint32_t w, const uint8_t* sessions, uint32_t session_
 int mpcxh_fac_verify_batch(uint32_t w, const uint8_t* sessions, uint32_t session_len, const uint32_t* N0,
                            const uint32_t* NCap, const uint32_t* s, const uint32_t* t, uint32_t count,
                            const uint32_t* pf, const uint8_t* v_neg, uint8_t* ok);
+
+/* ---------------------------------------------------------------- Feldman VSS
+ * Batched mirror of tss-lib v2.0.2's up:crypto/vss/feldman_vss.go at any
+ * threshold t with t + 1 <= 16 (csrc/host/vss.hpp; restated as recalled:
+ * upstream, verify), for keygen rounds 2-3 and resharing rounds 4-5
+ * (/root/reference/pkg/mpc/ecdsa_keygen_session.go:84,
+ * /root/reference/pkg/mpc/ecdsa_resharing_session.go). The point sums run on the
+ * GPU (mpcx_ec_msm_batch), so every call but the reconstruction needs a bound
+ * device. Ids are id_words (1..16) little-endian words each -- mpcium's party
+ * keys are SetBytes(nodeID + ":" + label), ~360 bits
+ * (/root/reference/pkg/mpc/node.go:43) -- and are used mod q, the group order.
+ * Scalars are 8 words, points 16 words (x, y; all-zero = infinity). A call
+ * takes 1..16 ids; an id that is 0 mod q or two ids equal mod q (CheckIndexes)
+ * and every limit above are MPCX_EINVAL.
+ *
+ * vss.Create for `count` secrets over the same n_ids ids (threshold < n_ids):
+ * a_0 = secret, a_1..a_t = GetRandomPositiveInt(readers[i], q) in that order;
+ * vs[i][k] = a_k G, shares[i][j] = sum_k a_k id_j^k mod q. */
+int mpcxh_vss_create_batch(uint32_t threshold, uint32_t n_ids, const uint32_t* ids, uint32_t id_words,
+                           uint32_t count, const uint32_t* secrets /* count x 8 */, const mpcxh_reader_t* readers,
+                           uint32_t* vs /* count x (t+1) x 16 */, uint32_t* shares /* count x n_ids x 8 */);
+/* (*Share).Verify for `count` (Vs, id, share) items: ok[i] = share_i G ==
+ * sum_k id_i^k V_ik. ok[i] = 0 without failing the call when n_vs != t + 1, a
+ * V_ik is infinity or not on the curve (crypto.NewECPoint refuses it), or id_i
+ * is 0 mod q. */
+int mpcxh_vss_verify_batch(uint32_t threshold, uint32_t count, uint32_t n_vs, const uint32_t* vs /* count x n_vs x 16 */,
+                           const uint32_t* ids /* count x id_words */, uint32_t id_words,
+                           const uint32_t* shares /* count x 8 */, uint8_t* ok);
+/* Keygen round 3 / resharing round 4-5's public shares for `count` sessions of
+ * the same n_parties ids: vc[s][k] = sum_i vs[s][i][k] (vc[s][0] is the
+ * wallet's public key), xs[s][j] = sum_k id_j^k vc[s][k] (BigXj). */
+int mpcxh_vss_public_shares_batch(uint32_t threshold, uint32_t n_parties, const uint32_t* ids, uint32_t id_words,
+                                  uint32_t count, const uint32_t* vs /* count x n_parties x (t+1) x 16 */,
+                                  uint32_t* vc /* count x (t+1) x 16 */, uint32_t* xs /* count x n_parties x 16 */);
+/* (Shares).ReConstruct for `count` items of n_shares (id, share) pairs each
+ * (ids: count x n_shares x id_words, shares: count x n_shares x 8): Lagrange
+ * interpolation at 0, on the host (no device needed). ok[i] = 0 and secret 0 on
+ * an id that is 0 mod q or two ids equal mod q. */
+int mpcxh_vss_reconstruct_batch(uint32_t count, uint32_t n_shares, const uint32_t* ids, uint32_t id_words,
+                                const uint32_t* shares, uint32_t* secrets /* count x 8 */, uint8_t* ok);
 
 /* Config-4 driver: one GG18 signature for each of `wallets` wallets, signed by
  * the first `signers` of `n_nodes` nodes (keys: Paillier private keys + own

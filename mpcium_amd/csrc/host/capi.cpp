@@ -22,6 +22,7 @@
 #include "safeprime.hpp"
 #include "keygenload.hpp"
 #include "signing.hpp"
+#include "vss.hpp"
 
 using namespace mpcx::host;
 
@@ -629,6 +630,97 @@ int mpcxh_secp_lincomb(const uint32_t* u1, const uint32_t* p16, const uint32_t* 
   return guard([&] {
     const auto P = points_from(p16, 1)[0];
     point_out(secp::LinComb(Nat::from_words(u1, w), P, Nat::from_words(u2, w)), out16);
+  });
+}
+
+// a point of the wire as it stands: all-zero = infinity, anything else as given
+// (vss::VerifyBatch decides whether it is on the curve)
+static secp::Affine point_in(const uint32_t* p16) {
+  secp::Affine a;
+  uint32_t o = 0;
+  for (int i = 0; i < 16; ++i) o |= p16[i];
+  if (!o) return a;
+  a.x = secp::NatToFe(Nat::from_words(p16, 8));
+  a.y = secp::NatToFe(Nat::from_words(p16 + 8, 8));
+  a.inf = false;
+  return a;
+}
+
+static void check_vss_args(uint32_t threshold, uint32_t n_ids, uint32_t id_words) {
+  if (threshold >= vss::kMaxTerms) throw std::invalid_argument("vss: threshold + 1 > 16");
+  if (n_ids < 1 || n_ids > vss::kMaxTerms) throw std::invalid_argument("vss: 1..16 ids per call");
+  if (id_words < 1 || id_words > 16) throw std::invalid_argument("vss: id_words outside [1, 16]");
+}
+
+int mpcxh_vss_create_batch(uint32_t threshold, uint32_t n_ids, const uint32_t* ids, uint32_t id_words, uint32_t count,
+                           const uint32_t* secrets, const mpcxh_reader_t* rdr, uint32_t* vs, uint32_t* shares) {
+  return guard([&] {
+    check_vss_args(threshold, n_ids, id_words);
+    if (threshold >= n_ids) throw std::invalid_argument("vss: threshold >= number of ids");
+    if (!ids || (count && (!secrets || !vs || !shares))) throw std::invalid_argument("null buffer");
+    std::vector<CounterDRBG> drbgs;
+    const auto rd = readers(rdr, count, &drbgs);
+    const auto out = vss::CreateBatch(threshold, nats(ids, id_words, n_ids), nats(secrets, 8, count), rd);
+    for (uint32_t s = 0; s < count; ++s) {
+      for (uint32_t k = 0; k <= threshold; ++k) point_out(out[s].Vs[k], vs + ((size_t)s * (threshold + 1) + k) * 16);
+      for (uint32_t j = 0; j < n_ids; ++j) out[s].shares[j].to_words(shares + ((size_t)s * n_ids + j) * 8, 8);
+    }
+  });
+}
+
+int mpcxh_vss_verify_batch(uint32_t threshold, uint32_t count, uint32_t n_vs, const uint32_t* vs, const uint32_t* ids,
+                           uint32_t id_words, const uint32_t* shares, uint8_t* ok) {
+  return guard([&] {
+    check_vss_args(threshold, 1, id_words);
+    if (n_vs > vss::kMaxTerms) throw std::invalid_argument("vss: n_vs > 16");
+    if (count && ((n_vs && !vs) || !ids || !shares || !ok)) throw std::invalid_argument("null buffer");
+    std::vector<vss::VerifyItem> items(count);
+    for (uint32_t i = 0; i < count; ++i) {
+      items[i].Vs.resize(n_vs);
+      for (uint32_t k = 0; k < n_vs; ++k) items[i].Vs[k] = point_in(vs + ((size_t)i * n_vs + k) * 16);
+      items[i].id = Nat::from_words(ids + (size_t)i * id_words, id_words);
+      items[i].share = Nat::from_words(shares + (size_t)i * 8, 8);
+    }
+    const auto r = vss::VerifyBatch(threshold, items);
+    std::copy(r.begin(), r.end(), ok);
+  });
+}
+
+int mpcxh_vss_public_shares_batch(uint32_t threshold, uint32_t n_parties, const uint32_t* ids, uint32_t id_words,
+                                  uint32_t count, const uint32_t* vs, uint32_t* vc, uint32_t* xs) {
+  return guard([&] {
+    check_vss_args(threshold, n_parties, id_words);
+    if (!ids || (count && (!vs || !vc || !xs))) throw std::invalid_argument("null buffer");
+    const uint32_t t1 = threshold + 1;
+    std::vector<std::vector<std::vector<secp::Affine>>> V(count);
+    for (uint32_t s = 0; s < count; ++s) {
+      V[s].assign(n_parties, std::vector<secp::Affine>(t1));
+      for (uint32_t i = 0; i < n_parties; ++i)
+        for (uint32_t k = 0; k < t1; ++k) V[s][i][k] = point_in(vs + (((size_t)s * n_parties + i) * t1 + k) * 16);
+    }
+    const auto out = vss::PublicSharesBatch(threshold, nats(ids, id_words, n_parties), V);
+    for (uint32_t s = 0; s < count; ++s) {
+      for (uint32_t k = 0; k < t1; ++k) point_out(out[s].Vc[k], vc + ((size_t)s * t1 + k) * 16);
+      for (uint32_t j = 0; j < n_parties; ++j) point_out(out[s].X[j], xs + ((size_t)s * n_parties + j) * 16);
+    }
+  });
+}
+
+int mpcxh_vss_reconstruct_batch(uint32_t count, uint32_t n_shares, const uint32_t* ids, uint32_t id_words,
+                                const uint32_t* shares, uint32_t* secrets, uint8_t* ok) {
+  return guard([&] {
+    check_vss_args(0, n_shares, id_words);
+    if (count && (!ids || !shares || !secrets || !ok)) throw std::invalid_argument("null buffer");
+    std::vector<std::vector<Nat>> I(count), S(count);
+    for (uint32_t i = 0; i < count; ++i) {
+      I[i] = nats(ids + (size_t)i * n_shares * id_words, id_words, n_shares);
+      S[i] = nats(shares + (size_t)i * n_shares * 8, 8, n_shares);
+    }
+    const auto r = vss::ReconstructBatch(I, S);
+    for (uint32_t i = 0; i < count; ++i) {
+      r[i].secret.to_words(secrets + (size_t)i * 8, 8);
+      ok[i] = r[i].ok ? 1 : 0;
+    }
   });
 }
 

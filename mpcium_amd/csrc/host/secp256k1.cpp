@@ -558,4 +558,50 @@ std::vector<Affine> CombineBatch(const std::vector<Comb>& items) {
   return out;
 }
 
+std::vector<Affine> MsmBatch(const std::vector<Msm>& items) {
+  MPCX_TRACE("gpu.ec", items.size());
+  MPCX_PROF("ec.msm_batch");
+  const size_t n = items.size();
+  std::vector<Affine> out(n);
+  if (!n) return out;
+  size_t np = 1;
+  for (const Msm& t : items) {
+    if (t.b.size() != t.P.size()) throw std::invalid_argument("MsmBatch: scalars and points differ in number");
+    np = std::max(np, t.b.size());
+  }
+  if (np > MPCX_EC_MSM_MAX_POINTS) throw std::invalid_argument("MsmBatch: more than 16 points in an item");
+  // one GPU thread per item (mpcx_ec_msm_batch, libmpcx's k_ec_msm)
+  std::vector<uint32_t> av(n * 8, 0), sc(n * np * 8, 0), pt(n * np * 16, 0), res(n * 16, 0);
+  auto put_scalar = [&](const Nat& k, uint32_t* w) {
+    if (k.bit_len() > 256) (k % CurveN()).to_words(w, 8);
+    else k.to_words(w, 8);
+  };
+  parallel_for((n + 255) / 256, [&](size_t blk) {
+    for (size_t i = blk * 256; i < std::min(n, blk * 256 + 256); ++i) {
+      const Msm& t = items[i];
+      put_scalar(t.a, &av[i * 8]);
+      for (size_t k = 0; k < t.b.size(); ++k) {
+        put_scalar(t.b[k], &sc[(i * np + k) * 8]);
+        if (t.P[k].inf) continue;  // all zero = infinity
+        FeToNat(t.P[k].x).to_words(&pt[(i * np + k) * 16], 8);
+        FeToNat(t.P[k].y).to_words(&pt[(i * np + k) * 16 + 8], 8);
+      }
+    }
+  });
+  const int rc = mpcx_ec_msm_batch((uint32_t)n, (uint32_t)np, av.data(), sc.data(), pt.data(), res.data());
+  if (rc != MPCX_OK) throw std::runtime_error(std::string("mpcx_ec_msm_batch: ") + mpcx_last_error());
+  parallel_for((n + 255) / 256, [&](size_t blk) {
+    for (size_t i = blk * 256; i < std::min(n, blk * 256 + 256); ++i) {
+      const uint32_t* w = &res[i * 16];
+      uint32_t o = 0;
+      for (int k = 0; k < 16; ++k) o |= w[k];
+      if (!o) continue;  // infinity
+      out[i].x = NatToFe(Nat::from_words(w, 8));
+      out[i].y = NatToFe(Nat::from_words(w + 8, 8));
+      out[i].inf = false;
+    }
+  });
+  return out;
+}
+
 }  // namespace mpcx::host::secp

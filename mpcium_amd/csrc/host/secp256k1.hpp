@@ -47,6 +47,15 @@ struct Comb {
 // Combine over a batch of independent items, on the GPU (one thread per item:
 // mpcx_ec_combine_batch); throws without a bound device
 std::vector<Affine> CombineBatch(const std::vector<Comb>& items);
+struct Msm {
+  Nat a;  // scalar of G (zero: no G term)
+  std::vector<Nat> b;
+  std::vector<Affine> P;  // b.size() points, at most 16
+};
+// a*G + sum_k b_k*P_k over a batch of independent items, on the GPU (one thread
+// per item: mpcx_ec_msm_batch). Scalars are reduced mod n; items are padded to
+// the batch's widest with zero scalars and infinity; throws without a bound device
+std::vector<Affine> MsmBatch(const std::vector<Msm>& items);
 bool IsOnCurve(const Affine& P);
 bool Equal(const Affine& P, const Affine& Q);
 

@@ -65,6 +65,8 @@ hipError_t mpcx_launch_sieve(const mpcx::SieveArgs* a, hipStream_t st);
 hipError_t mpcx_launch_selftest(uint32_t* d_out, hipStream_t st);
 hipError_t mpcx_launch_ec_combine(const uint32_t* sc, const uint32_t* pts, uint32_t* out, const uint32_t* gtab,
                                   uint32_t* ws, uint32_t count, hipStream_t st);
+hipError_t mpcx_launch_ec_msm(const uint32_t* a, const uint32_t* sc, const uint32_t* pts, uint32_t* out,
+                              const uint32_t* gtab, uint32_t* ws, uint32_t count, uint32_t n_points, hipStream_t st);
 hipError_t mpcx_launch_ec_probe(uint32_t op, const uint32_t* a, const uint32_t* b, uint32_t* out, uint32_t count,
                                 hipStream_t st);
 }
@@ -128,6 +130,7 @@ int g_fb_window = MPCX_FB_WINDOW_BITS;  // mpcx_set_option("fb_window", w): fixe
 #endif
 int g_fb_split = MPCX_FB_SPLIT_DEFAULT;  // mpcx_set_option("fb_split", s): comb waves per workgroup (0: by size)
 uint32_t g_split_min = 4096;             // mpcx_set_option("device_split_min", n): operands per device slice
+int g_ec_msm_ws_mb = 512;                // mpcx_set_option("ec_msm_ws_mb", mb): k_ec_msm table workspace per launch
 bool g_dup_device = false;               // mpcx_set_option("duplicate_device", 1): test hook, see below
 #ifndef MPCX_MX_DEFAULT
 #define MPCX_MX_DEFAULT 1
@@ -1650,6 +1653,8 @@ int mpcx_get_option(const char* key, int* value) {
     *value = g_fb_split;
   } else if (std::strcmp(key, "lanes") == 0) {
     *value = g_lanes.load();
+  } else if (std::strcmp(key, "ec_msm_ws_mb") == 0) {
+    *value = g_ec_msm_ws_mb;
   } else {
     return fail(MPCX_EINVAL, "option %s cannot be read", key);
   }
@@ -1726,6 +1731,10 @@ int mpcx_set_option(const char* key, int value) {
   } else if (std::strcmp(key, "kernel_stats") == 0) {
     // time every batch-entry-point kernel with an event pair (mpcx_kernel_stats)
     g_kstats = value != 0;
+  } else if (std::strcmp(key, "ec_msm_ws_mb") == 0) {
+    // test hook: cap, in MB, on the table workspace of one k_ec_msm launch (at least one block runs)
+    if (value < 1 || value > 4096) return fail(MPCX_EINVAL, "ec_msm_ws_mb %d outside [1, 4096]", value);
+    g_ec_msm_ws_mb = value;
   } else if (std::strcmp(key, "device_split_min") == 0) {
     // smallest per-device slice of a host-buffer batch split across the bound GPUs (0: never split)
     if (value < 0) return fail(MPCX_EINVAL, "device_split_min %d < 0", value);
@@ -2500,6 +2509,65 @@ int mpcx_ec_combine_batch(uint32_t count, const uint32_t* scalars, const uint32_
   if (!scalars || !points || !out) return fail(MPCX_EINVAL, "null buffer");
   return run_sliced(count, g_split_min, [&](int di, uint32_t first, uint32_t n) {
     return ec_range(di, n, scalars + (size_t)first * 24u, points + (size_t)first * 32u, out + (size_t)first * 16u);
+  });
+}
+
+namespace {
+// k_ec_msm's per-thread tables: 15 Jacobian entries of 24 words per point, 64 lanes per block
+constexpr size_t kEcMsmPointBytes = 15u * 24u * 64u * 4u;
+
+int ec_msm_range(int di, uint32_t count, uint32_t n_points, const uint32_t* a, const uint32_t* scalars,
+                 const uint32_t* points, uint32_t* out) {
+  Device& d = g_devs[di];
+  std::unique_lock<std::mutex> lk;
+  Lane& l = acquire_lane(d, lk);
+  LaneDrain drain(l);
+  int rc;
+  if ((rc = lane_stream(l))) return rc;
+  const uint32_t* gtab = nullptr;
+  if ((rc = ec_gtab(d, l, &gtab))) return rc;
+  // consecutive launches of at most per_launch blocks keep the tables under the cap; one block always runs
+  const size_t block_bytes = (size_t)n_points * kEcMsmPointBytes;
+  const uint32_t blocks = (count + 63u) / 64u;
+  const uint32_t per_launch =
+      (uint32_t)std::min<size_t>(blocks, std::max<size_t>(1, ((size_t)g_ec_msm_ws_mb << 20) / block_bytes));
+  const size_t ab = a ? (size_t)count * 8u * 4u : 0, sb = (size_t)count * n_points * 8u * 4u,
+               pb = (size_t)count * n_points * 16u * 4u, ob = (size_t)count * 16u * 4u;
+  if ((rc = ensure_buffer(l.stage[0], sb)) || (rc = ensure_buffer(l.stage[1], pb)) ||
+      (rc = ensure_buffer(l.stage[2], ob)) || (a && (rc = ensure_buffer(l.stage[3], ab))) ||
+      (rc = ensure_workspace(l, (size_t)per_launch * block_bytes)))
+    return rc;
+  if ((rc = h2d(l, l.stage[0].ptr, scalars, sb)) || (rc = h2d(l, l.stage[1].ptr, points, pb)) ||
+      (a && (rc = h2d(l, l.stage[3].ptr, a, ab))))
+    return rc;
+  const uint32_t *d_sc = (const uint32_t*)l.stage[0].ptr, *d_pt = (const uint32_t*)l.stage[1].ptr,
+                 *d_a = a ? (const uint32_t*)l.stage[3].ptr : nullptr;
+  uint32_t* d_out = (uint32_t*)l.stage[2].ptr;
+  for (uint32_t b0 = 0; b0 < blocks; b0 += per_launch) {
+    const uint32_t first = b0 * 64u, n = std::min(count - first, per_launch * 64u);
+    const int ks = kstat_begin(l);
+    hipError_t e = mpcx_launch_ec_msm(d_a ? d_a + (size_t)first * 8u : nullptr, d_sc + (size_t)first * n_points * 8u,
+                                      d_pt + (size_t)first * n_points * 16u, d_out + (size_t)first * 16u, gtab, l.ws,
+                                      n, n_points, l.st);
+    if (e != hipSuccess) return hip_fail(e, "launch k_ec_msm");
+    kstat_end(l, ks, d, di, "ec_msm", -1, n, 0.0);
+    d.launches.fetch_add(1, std::memory_order_relaxed);
+    launch_log("ec_msm", -1, n, 256, 256, 0.0);
+  }
+  return d2h_sync(out, l.stage[2].ptr, ob, l);
+}
+}  // namespace
+
+int mpcx_ec_msm_batch(uint32_t count, uint32_t n_points, const uint32_t* a, const uint32_t* scalars,
+                      const uint32_t* points, uint32_t* out) {
+  if (n_points < 1 || n_points > MPCX_EC_MSM_MAX_POINTS)
+    return fail(MPCX_EINVAL, "n_points %u outside [1, %d]", n_points, MPCX_EC_MSM_MAX_POINTS);
+  if (!scalars || !points || !out) return fail(MPCX_EINVAL, "null buffer");
+  if (count == 0) return MPCX_OK;
+  return run_sliced(count, g_split_min, [&](int di, uint32_t first, uint32_t n) {
+    return ec_msm_range(di, n, n_points, a ? a + (size_t)first * 8u : nullptr,
+                        scalars + (size_t)first * n_points * 8u, points + (size_t)first * n_points * 16u,
+                        out + (size_t)first * 16u);
   });
 }
 

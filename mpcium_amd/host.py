@@ -74,6 +74,10 @@ SIGNATURES = [
     ("mpcxh_drbg_read", _i, [_u64, _vp, ctypes.c_size_t]),
     ("mpcxh_go_rand_int63", _i, [ctypes.c_int64, _u32, _vp]),
     ("mpcxh_go_mr_bases", _i, [_vp, _u32, _u32, _vp]),
+    ("mpcxh_vss_create_batch", _i, [_u32, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
+    ("mpcxh_vss_verify_batch", _i, [_u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp]),
+    ("mpcxh_vss_public_shares_batch", _i, [_u32, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
+    ("mpcxh_vss_reconstruct_batch", _i, [_u32, _u32, _vp, _u32, _vp, _vp, _vp]),
 ]
 
 ERR_OK, ERR_MESSAGE_TOO_LONG, ERR_MESSAGE_MALFORMED = 0, 1, 2

@@ -59,6 +59,7 @@ SIGNATURES = [
                                          ctypes.c_uint32]),
     ("mpcx_fermat2_batch", ctypes.c_int, [ctypes.c_uint32, _vp, ctypes.c_uint32, _vp]),
     ("mpcx_ec_combine_batch", ctypes.c_int, [ctypes.c_uint32, _vp, _vp, _vp]),
+    ("mpcx_ec_msm_batch", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
     ("mpcx_ec_probe", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp]),
     ("mpcx_modexp_multi_batch", ctypes.c_int, [ctypes.c_uint32, _vp]),
     ("mpcx_mr_batch", ctypes.c_int, [ctypes.c_uint32, _vp, ctypes.c_uint32, _vp, _vp]),
@@ -531,6 +532,42 @@ def ec_combine_batch(items) -> list:
     for v in words_to_ints(out):
         res.append(None if v == 0 else (v & mask, v >> 256))
     return res
+
+
+EC_MSM_MAX_POINTS = 16
+
+
+def ec_msm_batch(items) -> list:
+    """secp256k1 a G + sum_k b_k P_k per item (a, [(b_k, P_k), ...]), a an
+    integer or None (no item of the batch has a G term when every a is None),
+    points as (x, y) tuples or None (infinity) -> list of (x, y) or None.
+    Scalars are any integers, taken mod the group order n; items with fewer
+    terms than the batch's widest are padded with zero scalars and infinity."""
+    n = len(items)
+    if n == 0:
+        return []
+    k = max(1, max(len(terms) for _, terms in items))
+    if k > EC_MSM_MAX_POINTS:
+        raise ValueError(f"an item has {k} terms > {EC_MSM_MAX_POINTS}")
+    with_a = any(a is not None for a, _ in items)
+    av = np.zeros((n, 8), dtype="<u4")
+    sc = np.zeros((n, k * 8), dtype="<u4")
+    pt = np.zeros((n, k * 16), dtype="<u4")
+    mask = (1 << 256) - 1
+    for i, (a, terms) in enumerate(items):
+        if a is not None:
+            av[i] = int_to_words(a % SECP_N, 8)
+        s = p = 0
+        for j, (b, P) in enumerate(terms):
+            s |= (b % SECP_N) << (256 * j)
+            if P is not None:
+                p |= (P[0] | (P[1] << 256)) << (512 * j)
+        sc[i] = int_to_words(s, k * 8)
+        pt[i] = int_to_words(p, k * 16)
+    out = np.zeros((n, 16), dtype="<u4")
+    _check(lib().mpcx_ec_msm_batch(n, k, av.ctypes.data if with_a else None, sc.ctypes.data, pt.ctypes.data,
+                                   out.ctypes.data))
+    return [None if v == 0 else (v & mask, v >> 256) for v in words_to_ints(out)]
 
 
 EC_OPS = {"add": 0, "sub": 1, "mul": 2, "sqr": 3, "inv": 4, "jac_dbl": 5, "jac_add": 6, "jac_madd": 7}

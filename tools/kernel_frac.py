@@ -21,6 +21,8 @@ GEOM = {0: (1, 37, 64), 1: (4, 19, 16), 2: (4, 37, 16), 3: (16, 5, 4), 4: (32, 5
 def kname(kind, geom):
     if kind == "ec_combine":
         return "k_ec_combine"
+    if kind == "ec_msm":
+        return "k_ec_msm"
     P, K, G = GEOM[geom]
     return f"k_{kind}<{P}, {K}, {G},"
 
