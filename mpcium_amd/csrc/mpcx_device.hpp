@@ -901,7 +901,8 @@ __device__ __forceinline__ void modexp_nsq_wave(const ModexpArgs& a, const uint3
   lds_store_digits<K>(ga, p, V);
   wave_lds_fence();
   auto digit = [&](uint32_t d) __attribute__((always_inline)) -> uint32_t {
-    return d < (uint32_t)L ? gb[d] : (d < 2u * L ? ga[d - L] : 0u);
+    // row b: the product loop's low words, the digit in bits 0..27 (mx_product)
+    return d < (uint32_t)L ? gb[d] & M28 : (d < 2u * L ? ga[d - L] : 0u);
   };
   if (p == 0) {  // one lane per operand, once per exponentiation: y - N^2 if y >= N^2
     constexpr uint32_t L2 = (uint32_t)MPCX_GEOM_L(2);

@@ -62,19 +62,60 @@ __device__ __forceinline__ MxConsts mx_consts(const uint8_t* img, int lane) {
 }
 
 // radix-2^28 digit (two's complement, |x| < 2^28) -> 4 radix-2^7 digits, one per
-// byte (the top one signed): open a 1-bit gap above bits 6, 13 and 20
+// byte (the top one signed), in five instructions: a 2-bit gap above bit 13 first
+// (x + 3 t for t = x's bits 14 and up, as a shift-add and a subtract), then the 1-bit
+// gaps above bits 6 and 22 of that with one mask and one add (no carry crosses the
+// halves: bits 14 and 15 are clear). Equal for every 32-bit x to the three
+// add-the-upper-part steps x += x & ~(2^7 - 1), ~(2^15 - 1), ~(2^23 - 1) it replaces
+// (six instructions; tests/test_mx_spread_cpu.py).
 // (round 6: the closed form x + 2^7 (x >> 7) + 2^15 (x >> 14) + 2^23 (x >> 21) on the
-// MAD pipe measured slower, profiles/r06/spab/)
+// MAD pipe measured slower, profiles/r06/spab/; round 8: x + 3 2^14 (x >> 14) as one
+// v_mad_i32_i24, four instructions, won alone and lost together with the unmasked
+// stores of the product loops, profiles/r08/valu/)
+//
+// The empty asm statements here, in mx_spread7_low28 and in mx_retire_mask emit no
+// instruction: they only hide a value's origin from hipcc, whose canonical forms of
+// these expressions are one instruction longer (no builtin states the shorter
+// shape). They cannot change a result, only the instruction count, and that rests on
+// this compiler's behaviour: with every ROCm upgrade regenerate the listing and
+// compare the counts with DESIGN.md 5.2i (tools/isa_loops.py, tools/isa_census.py).
 __device__ __forceinline__ uint32_t mx_spread7(uint32_t x) {
-  x += x & 0xFFFFFF80u;
-  x += x & 0xFFFF8000u;
-  x += x & 0xFF800000u;
+  uint32_t t = x & 0xFFFFC000u;
+  asm("" : "+v"(t));  // opaque: or hipcc rewrites x - t as x & 0x3FFF and is back at six
+  x = ((t << 2) + x) - t;
+  x += x & 0xFF80FF80u;
   return x;
+}
+// The same for a digit of T as the product loops store it: bits 0..27 are the
+// digit (>= 0), bits 28..31 whatever the column sum held above it. The two masks of
+// the 14 | 14 split drop those bits, so the loops store the low word unmasked
+// (five instructions here for one saved at each of the L stores).
+__device__ __forceinline__ uint32_t mx_spread7_low28(uint32_t x) {
+  uint32_t t = x & 0x0FFFC000u;
+  asm("" : "+v"(t));  // opaque: one v_lshl_add_u32; hipcc's own form is a shift and two bit operations
+  x = (t << 2) + (x & 0x00003FFFu);
+  x += x & 0xFF80FF80u;
+  return x;
+}
+
+// The retire step of the product loops hands a column's low 28 bits to the lane
+// below as its new top column, except across a group boundary: lane 0's digit
+// leaves the window and must not shift into the previous group's top slot. The
+// RECEIVING lane masks what it pulls through DPP (one v_and_b32 with a DPP source):
+// 2^28 - 1 inside a group, 0 in the group's top lane (lane 63 reads 0 anyway).
+template <int P>
+__device__ __forceinline__ uint32_t mx_retire_mask(int p) {
+  uint32_t m = p == P - 1 ? 0u : M28;
+  asm volatile("" : "+v"(m));  // opaque: or the select comes back into every retire step
+  return m;
 }
 
 // T = A * B (B == A for SQR; B2IN: the row holds 2B) in montmul's row loop without
 // the m_i N half: T's low L digits are emitted to tl[] as the window passes them
 // (lane p == 0 of the group), the high L digits end in A (<= 2^28 + 2^10).
+// A word of tl[] is the retiring column's low 32 bits: T's digit (< 2^28) in bits
+// 0..27 and the low bits of its carry above. Every reader drops them: the fragment
+// build (mx_spread7_low28) and ttop in mx_reduce, digit() at k_modexp_nsq's exit.
 //
 // Every lane stores, lanes p != 0 into a per-lane trash slot of the wave's LDS
 // area (tr: that lane's slots, L words from lane + 0), so that the loop body has
@@ -87,6 +128,7 @@ __device__ __forceinline__ void mx_product(uint32_t (&A)[K], const uint32_t* bl,
 #pragma unroll
   for (int k = 0; k < K; ++k) acc[k] = 0;
   uint32_t bnext = bl[0];
+  const uint32_t rmask = mx_retire_mask<P>(p);
 #pragma nounroll
   for (int o = 0; o < P; ++o) {
     const uint32_t* bo = bl + o * K;
@@ -113,11 +155,10 @@ __device__ __forceinline__ void mx_product(uint32_t (&A)[K], const uint32_t* bl,
       });
       const uint64_t a0 = acc[u];
       acc[(u + 1) % K] += a0 >> DB;
-      // lane 0's digit leaves the window as T's digit i (in CIOS it is zero);
-      // it must not shift into the previous group's top slot
-      const uint32_t lo = (uint32_t)a0 & M28;
-      to[u] = lo;
-      acc[u] = from_next_lane(p == 0 ? 0u : lo);
+      // lane 0's digit leaves the window as T's digit i (in CIOS it is zero): the
+      // low word as it is, bits 28..31 are the readers' to drop (above mx_product)
+      to[u] = (uint32_t)a0;
+      acc[u] = from_next_lane((uint32_t)a0) & rmask;
     });
   }
   carry_pass64<P, K>(acc);
@@ -130,7 +171,8 @@ __device__ __forceinline__ void mx_product(uint32_t (&A)[K], const uint32_t* bl,
 
 // Z = U * B + V * A for the rows A (al) and B (bl) in ONE row loop (2 K MADs per row
 // step; k_modexp_nsq's cross term u v' + v u'): Z's low L digits overwrite row B
-// behind the digits the loop has read, the high L digits end in V (<= 2^28 + 2^10).
+// behind the digits the loop has read (as mx_product's: the digit in bits 0..27 of
+// the word), the high L digits end in V (<= 2^28 + 2^10).
 // Accumulators: 2 K products < 2^56.001 between two restarts, < 2^61.3 for K = 19.
 template <int P, int K>
 __device__ __forceinline__ void mx_product2(const uint32_t (&U)[K], uint32_t (&V)[K], const uint32_t* al,
@@ -139,6 +181,7 @@ __device__ __forceinline__ void mx_product2(const uint32_t (&U)[K], uint32_t (&V
 #pragma unroll
   for (int k = 0; k < K; ++k) acc[k] = 0;
   uint32_t anext = al[0], bnext = bl[0];
+  const uint32_t rmask = mx_retire_mask<P>(p);
 #pragma nounroll
   for (int o = 0; o < P; ++o) {
     const uint32_t* ao = al + o * K;
@@ -156,9 +199,8 @@ __device__ __forceinline__ void mx_product2(const uint32_t (&U)[K], uint32_t (&V
       });
       const uint64_t a0 = acc[u];
       acc[(u + 1) % K] += a0 >> DB;
-      const uint32_t lo = (uint32_t)a0 & M28;
-      to[u] = lo;
-      acc[u] = from_next_lane(p == 0 ? 0u : lo);
+      to[u] = (uint32_t)a0;
+      acc[u] = from_next_lane((uint32_t)a0) & rmask;
     });
   }
   carry_pass64<P, K>(acc);
@@ -203,6 +245,8 @@ __device__ __forceinline__ void mx_toeplitz(mx_v4i (&acc)[O1 - O0], const uint8_
   auto ld = [&](int j) __attribute__((always_inline)) {
     return *reinterpret_cast<const mx_v4i*>(f + 16 * (S::JMAX - j));
   };
+  // (hipcc folds this zero fill into the first MFMA of each block as the inline
+  // constant 0 for C: no v_mov is issued for it)
   if constexpr (!ACCUM) static_for<0, O1 - O0>([&](auto oc) { acc[decltype(oc)::value] = mx_v4i{0, 0, 0, 0}; });
   // first and last Toeplitz block with an MFMA in this chunk
   constexpr int JLO = (O0 - 4 * (S::KB - 1)) > 0 ? (O0 - 4 * (S::KB - 1)) : 0;
@@ -377,10 +421,10 @@ __device__ __forceinline__ void mx_reduce(uint32_t (&A)[S::K], uint32_t* rows, c
           if (16 * kb + 4 * h + i >= L) v[i] = 0;
       }
 #pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = (int)mx_spread7((uint32_t)v[i]);
+      for (int i = 0; i < 4; ++i) v[i] = (int)mx_spread7_low28((uint32_t)v[i]);
       bf[s][kb] = v;
     });
-    ttop[s] = (int)rn[L - 1];
+    ttop[s] = (int)(rn[L - 1] & M28);
   });
   wave_lds_fence();
   MX_STAMP(2);
