@@ -272,6 +272,32 @@ int mpcx_ec_msm_batch(uint32_t count, uint32_t n_points,
                       const uint32_t* points,   /* count x n_points x 16 words (x, y); all-zero = infinity */
                       uint32_t* out);           /* count x 16 words; all-zero = infinity */
 
+#define MPCX_ED_MSM_MAX_POINTS 16
+/* Ed25519 (twisted Edwards, -x^2 + y^2 = 1 + d x^2 y^2 over p = 2^255 - 19,
+ * base point B of RFC 8032): out_i = a_i B + sum_{k < n_points} b_ik P_ik for
+ * count independent items, one GPU thread each (k_ed_msm: Straus, 4-bit
+ * windows, complete extended-coordinate additions) -- the point equations of
+ * tss-lib's threshold EdDSA (up:eddsa/signing: R_i = r_i B, the Schnorr check
+ * t B - c R_j, R = sum R_j) and of edwards.Verify (s B - h A).
+ * 0 <= n_points <= MPCX_ED_MSM_MAX_POINTS, the same for every item;
+ * n_points == 0 is the plain a_i B and needs a. Scalars are 8 little-endian
+ * words, any 256-bit value, used as integers (not reduced mod the group order
+ * L: no difference for a point of order L, and defined for the small-order
+ * points). Points are affine x, y, 8 little-endian words each, both < p and on
+ * the curve (the caller checks, as crypto.NewECPoint does; there is no
+ * decompression on the device). A term whose scalar is zero or whose point is
+ * all-zero is dropped. The result is affine; the identity comes out as (0, 1).
+ * The table workspace per launch is capped by "ec_msm_ws_mb" as for
+ * mpcx_ec_msm_batch (122,880 B per 64-item block and point). The argument
+ * checks come before any device is touched: n_points out of range, a null
+ * out, a null scalars or points with n_points > 0, or n_points == 0 with a
+ * null a is MPCX_EINVAL; count == 0 is then MPCX_OK. */
+int mpcx_ed_msm_batch(uint32_t count, uint32_t n_points,
+                      const uint32_t* a,        /* count x 8 words, or NULL: no B term */
+                      const uint32_t* scalars,  /* count x n_points x 8 words */
+                      const uint32_t* points,   /* count x n_points x 16 words (x, y); all-zero = no term */
+                      uint32_t* out);           /* count x 16 words (x, y) */
+
 /* Miller-Rabin: ok[i] = n_i is a strong probable prime to base bases[i]
  * (5 <= n_i < 2^1024 odd, bases[i] < 2^(32*n_words); a base that is 0 mod
  * n_i reports "composite"). Each candidate is its own modulus. Serves
@@ -464,7 +490,9 @@ int mpcx_sync(void* stream);
  *   "ec_msm_ws_mb" 1..4096 (default 512): cap, in MB, on the per-thread table
  *                workspace of one k_ec_msm launch (92,160 B per 64-item block
  *                and point); mpcx_ec_msm_batch cuts a device's slice into
- *                consecutive launches under it, never below one block.
+ *                consecutive launches under it, never below one block. The
+ *                same cap holds for k_ed_msm and mpcx_ed_msm_batch (122,880 B
+ *                per block and point).
  * Environment, read at mpcx_init / mpcx_init_devices: MPCX_LANES (1..8,
  * default 6: execution lanes per device), MPCX_GEOM_POLICY, MPCX_NARROW_ROUNDS,
  * MPCX_FB_WINDOW, MPCX_MX, MPCX_NSQ, MPCX_MX_STEP, MPCX_GEOM_TPUT. */
@@ -514,6 +542,31 @@ int mpcx_nsq_consts(const uint32_t* m_words, uint32_t m_len, uint32_t* out, size
 #define MPCX_EC_OP_JAC_ADD 6
 #define MPCX_EC_OP_JAC_MADD 7
 int mpcx_ec_probe(uint32_t op, uint32_t count, const uint32_t* a, const uint32_t* b, uint32_t* out);
+
+/* One Ed25519 field or point operation of k_ed_msm's device code
+ * (mpcium_amd/csrc/mpcx_ed_fe.hpp) per item, one GPU thread each, on the
+ * calling thread's selected device; for tests and tools. a, b, out: count x 32
+ * little-endian words per item -- an extended point X, Y, Z, T (x = X/Z,
+ * y = Y/Z, T = XY/Z), or a field element in the first 8 words:
+ *   ADD, SUB, MUL   out[0..8) = a[0..8) op b[0..8) mod p = 2^255 - 19
+ *   SQR, INV        out[0..8) = a^2, a^(p-2) mod p (b is not used)
+ *   ED_DBL          out = 2 a (b is not used; a.T is not read)
+ *   ED_ADD          out = a + b, both extended (unified, complete)
+ *   ED_MADD         out = a + the affine point whose entry (y + x, y - x,
+ *                   2 d x y) is b[0..24) (b[24..32) is not used)
+ * Field results leave out[8..32) zero. Point results are extended, not
+ * normalised. MPCX_EINVAL for an unknown op, a null buffer, or any of the eight
+ * 8-word input values of an item >= p (whether the op reads it or not): the
+ * device functions take values below p only. */
+#define MPCX_ED_OP_ADD 0
+#define MPCX_ED_OP_SUB 1
+#define MPCX_ED_OP_MUL 2
+#define MPCX_ED_OP_SQR 3
+#define MPCX_ED_OP_INV 4
+#define MPCX_ED_OP_ED_DBL 5
+#define MPCX_ED_OP_ED_ADD 6
+#define MPCX_ED_OP_ED_MADD 7
+int mpcx_ed_probe(uint32_t op, uint32_t count, const uint32_t* a, const uint32_t* b, uint32_t* out);
 
 /* Kernel-class geometry of a modulus (for benchmarks and roofline math):
  * digits L (radix 2^28), lanes per operand P, digits per lane K, operands per

@@ -27,6 +27,11 @@
  *   mpcxh_vss_public_shares_batch  up:ecdsa/keygen/round_3.go, up:ecdsa/resharing/round_4_new_step_2.go
  *                                (Vc = sum of the parties' Vs, BigXj = sum_k id_j^k Vc_k)
  *   mpcxh_vss_reconstruct_batch  up:crypto/vss/feldman_vss.go (Shares).ReConstruct
+ *   mpcxh_ed25519_decode_batch   RFC 8032 5.1.3 (decred edwards/v2 point decoding)
+ *   mpcxh_ed25519_hram_batch     SHA-512(R || A || M) mod L (up:eddsa/signing/round_3.go)
+ *   mpcxh_eddsa_verify_batch     decred edwards/v2 Verify, called at
+ *                                /root/reference/pkg/mpc/eddsa_signing_session.go
+ *   mpcxh_eddsa_sign_batch       up:eddsa/signing round_1.go .. finalize.go
  */
 #ifndef MPCX_HOST_H_
 #define MPCX_HOST_H_
@@ -273,6 +278,61 @@ int mpcxh_vss_public_shares_batch(uint32_t threshold, uint32_t n_parties, const 
  * an id that is 0 mod q or two ids equal mod q. */
 int mpcxh_vss_reconstruct_batch(uint32_t count, uint32_t n_shares, const uint32_t* ids, uint32_t id_words,
                                 const uint32_t* shares, uint32_t* secrets /* count x 8 */, uint8_t* ok);
+
+/* ---------------------------------------------------------------- EdDSA (Ed25519)
+ * The other protocol mpcium runs for every wallet: threshold EdDSA over Ed25519
+ * (tss-lib v2 up:eddsa/signing, /root/reference/pkg/mpc/eddsa_signing_session.go),
+ * every result checked with decred's edwards.Verify (csrc/host/ed25519.hpp,
+ * csrc/host/eddsa.hpp). Points are 16 words (affine x, y; the identity is
+ * (0, 1)), scalars 8 words, encodings 32 bytes (y little-endian, the sign of x
+ * in bit 255). Messages of a batch are variable-length byte strings given as
+ * count + 1 offsets into one buffer: item i is msgs[msg_off[i] .. msg_off[i+1]).
+ * A message is taken as given: mpcium signs tx.Bytes(), a big.Int's bytes,
+ * which drop leading zero bytes (mpcium_amd.eddsa.tx_message does the same).
+ *
+ * The first two entries are host-only (no device needed).
+ * RFC 8032 5.1.3 decoding of `count` encodings: ok[i] = 0 and xy[i] zero for
+ * y >= p, for a y with no x on the curve, and for x = 0 with the sign bit set. */
+int mpcxh_ed25519_decode_batch(uint32_t count, const uint8_t* enc /* count x 32 */, uint32_t* xy /* count x 16 */,
+                               uint8_t* ok);
+/* h[i] = SHA-512(R_i || A_i || M_i) mod L (the challenge of RFC 8032 and of
+ * up:eddsa/signing round 3). */
+int mpcxh_ed25519_hram_batch(uint32_t count, const uint8_t* R /* count x 32 */, const uint8_t* A /* count x 32 */,
+                             const uint8_t* msgs, const uint64_t* msg_off /* count + 1 */, uint32_t* h /* count x 8 */);
+/* What edwards.Verify decides for `count` (public key, message, signature)
+ * items: ok[i] = 1 iff the key is on the curve, s < L (RFC 8032 and OpenSSL;
+ * decred's behaviour for s >= L: upstream, verify) and enc(s B - h A) equals
+ * the signature's first 32 bytes byte for byte. One GPU batch
+ * (mpcx_ed_msm_batch: a = s, the point A with scalar L - h). */
+int mpcxh_eddsa_verify_batch(uint32_t count, const uint32_t* pk /* count x 16 */, const uint8_t* msgs,
+                             const uint64_t* msg_off /* count + 1 */, const uint8_t* sigs /* count x 64 */,
+                             uint8_t* ok);
+/* up:eddsa/signing rounds 1-3 and finalize for `count` wallets of n_signers
+ * (2..16) signers each, every signer replayed in process (csrc/host/eddsa.hpp
+ * gives the steps; draw order and hash inputs: upstream, verify). Per wallet:
+ * the signers' ids (id_words 1..16 words each, used mod L; zero or equal ids
+ * are MPCX_EINVAL), their Shamir shares, the public key, the message, the
+ * session bytes of the Schnorr proofs (session_len each; signer i uses
+ * session || big.Int(i).Bytes()) and one reader per signer. Every point
+ * equation of a step is one mpcx_ed_msm_batch over all wallets and signers.
+ * status[w] = 0 with sigs[w] = enc(R) || LE32(s), or the round that aborted the
+ * wallet (3: a decommitment or Schnorr proof failed; 4: the final
+ * verification) with sigs[w] zero; the other wallets are unaffected.
+ * trace_flags (or NULL) marks wallets to trace; trace receives, per flagged
+ * wallet in order, n_signers x 64 words -- r_i (8), R_i (16), the commitment
+ * (8), the proof's alpha (16) and t (8), s_i (8) -- then the 8-word
+ * SHA512_256i of the round transcript (eddsa.hpp). Test hooks: tamper_kind 1
+ * shifts signer 0's Schnorr response in wallet tamper_wallet, 2 swaps the
+ * coordinates of its decommitment; -1 / 0 for none. gpu_s (or NULL) receives
+ * the wall time spent inside the GPU batches. */
+int mpcxh_eddsa_sign_batch(uint32_t count, uint32_t n_signers, const uint32_t* ids /* count x n_signers x id_words */,
+                           uint32_t id_words, const uint32_t* shares /* count x n_signers x 8 */,
+                           const uint32_t* pk /* count x 16 */, const uint8_t* msgs,
+                           const uint64_t* msg_off /* count + 1 */, const uint8_t* sessions /* count x session_len */,
+                           uint32_t session_len, const mpcxh_reader_t* readers /* count x n_signers */,
+                           const uint8_t* trace_flags, int64_t tamper_wallet, int tamper_kind,
+                           uint8_t* sigs /* count x 64 */, uint8_t* status /* count */, uint32_t* trace,
+                           double* gpu_s);
 
 /* Config-4 driver: one GG18 signature for each of `wallets` wallets, signed by
  * the first `signers` of `n_nodes` nodes (keys: Paillier private keys + own

@@ -23,6 +23,7 @@
 #include "keygenload.hpp"
 #include "signing.hpp"
 #include "vss.hpp"
+#include "eddsa.hpp"
 
 using namespace mpcx::host;
 
@@ -721,6 +722,107 @@ int mpcxh_vss_reconstruct_batch(uint32_t count, uint32_t n_shares, const uint32_
       r[i].secret.to_words(secrets + (size_t)i * 8, 8);
       ok[i] = r[i].ok ? 1 : 0;
     }
+  });
+}
+
+// ---------------------------------------------------------------- EdDSA
+static ed::Point ed_point_in(const uint32_t* p16) {
+  ed::Point P;
+  P.x = Nat::from_words(p16, 8);
+  P.y = Nat::from_words(p16 + 8, 8);
+  return P;
+}
+static void check_offsets(const uint64_t* off, uint32_t count) {
+  for (uint32_t i = 0; i < count; ++i)
+    if (off[i + 1] < off[i]) throw std::invalid_argument("message offsets must not decrease");
+}
+
+int mpcxh_ed25519_decode_batch(uint32_t count, const uint8_t* enc, uint32_t* xy, uint8_t* ok) {
+  return guard([&] {
+    if (count && (!enc || !xy || !ok)) throw std::invalid_argument("null buffer");
+    parallel_for(count, [&](size_t i) {
+      ed::Point P;
+      uint32_t* o = xy + i * 16;
+      std::fill(o, o + 16, 0u);
+      ok[i] = ed::Decode(enc + i * 32, &P) ? 1 : 0;
+      if (ok[i]) {
+        P.x.to_words(o, 8);
+        P.y.to_words(o + 8, 8);
+      }
+    });
+  });
+}
+
+int mpcxh_ed25519_hram_batch(uint32_t count, const uint8_t* R, const uint8_t* A, const uint8_t* msgs,
+                             const uint64_t* msg_off, uint32_t* h) {
+  return guard([&] {
+    if (count && (!R || !A || !msg_off || !h)) throw std::invalid_argument("null buffer");
+    if (!count) return;
+    check_offsets(msg_off, count);
+    if (msg_off[count] > msg_off[0] && !msgs) throw std::invalid_argument("null buffer");
+    parallel_for(count, [&](size_t i) {
+      ed::Hram(R + i * 32, A + i * 32, msgs + msg_off[i], (size_t)(msg_off[i + 1] - msg_off[i])).to_words(h + i * 8, 8);
+    });
+  });
+}
+
+int mpcxh_eddsa_verify_batch(uint32_t count, const uint32_t* pk, const uint8_t* msgs, const uint64_t* msg_off,
+                             const uint8_t* sigs, uint8_t* ok) {
+  return guard([&] {
+    if (count && (!pk || !msg_off || !sigs || !ok)) throw std::invalid_argument("null buffer");
+    if (!count) return;
+    check_offsets(msg_off, count);
+    if (msg_off[count] > msg_off[0] && !msgs) throw std::invalid_argument("null buffer");
+    std::vector<eddsa::VerifyItem> items(count);
+    for (uint32_t i = 0; i < count; ++i) {
+      items[i].A = ed_point_in(pk + (size_t)i * 16);
+      if (msg_off[i + 1] > msg_off[i]) items[i].msg.assign(msgs + msg_off[i], msgs + msg_off[i + 1]);
+      std::memcpy(items[i].sig, sigs + (size_t)i * 64, 64);
+    }
+    const auto r = eddsa::VerifyBatch(items);
+    std::copy(r.begin(), r.end(), ok);
+  });
+}
+
+int mpcxh_eddsa_sign_batch(uint32_t count, uint32_t n_signers, const uint32_t* ids, uint32_t id_words,
+                           const uint32_t* shares, const uint32_t* pk, const uint8_t* msgs, const uint64_t* msg_off,
+                           const uint8_t* sessions, uint32_t session_len, const mpcxh_reader_t* rdr,
+                           const uint8_t* trace_flags, int64_t tamper_wallet, int tamper_kind, uint8_t* sigs,
+                           uint8_t* status, uint32_t* trace, double* gpu_s) {
+  return guard([&] {
+    if (n_signers < 2 || n_signers > eddsa::kMaxSigners) throw std::invalid_argument("eddsa: 2..16 signers per wallet");
+    if (id_words < 1 || id_words > 16) throw std::invalid_argument("eddsa: id_words outside [1, 16]");
+    if (tamper_kind < 0 || tamper_kind > eddsa::kTamperDecommit) throw std::invalid_argument("eddsa: unknown tamper kind");
+    if (count && (!ids || !shares || !pk || !msg_off || !rdr || !sigs || !status || (session_len && !sessions)))
+      throw std::invalid_argument("null buffer");
+    if (gpu_s) *gpu_s = 0;
+    if (!count) return;
+    check_offsets(msg_off, count);
+    if (msg_off[count] > msg_off[0] && !msgs) throw std::invalid_argument("null buffer");
+    size_t traced = 0;
+    for (uint32_t w = 0; trace_flags && w < count; ++w) traced += trace_flags[w] ? 1 : 0;
+    if (traced && !trace) throw std::invalid_argument("null trace buffer");
+    std::vector<CounterDRBG> drbgs;
+    const auto rd = readers(rdr, count * n_signers, &drbgs);
+    std::vector<eddsa::Wallet> ws(count);
+    for (uint32_t w = 0; w < count; ++w) {
+      eddsa::Wallet& x = ws[w];
+      x.ids = nats(ids + (size_t)w * n_signers * id_words, id_words, n_signers);
+      x.shares = nats(shares + (size_t)w * n_signers * 8, 8, n_signers);
+      x.pk = ed_point_in(pk + (size_t)w * 16);
+      if (msg_off[w + 1] > msg_off[w]) x.msg.assign(msgs + msg_off[w], msgs + msg_off[w + 1]);
+      if (session_len) x.session.assign(sessions + (size_t)w * session_len, sessions + (size_t)(w + 1) * session_len);
+      x.readers.assign(rd.begin() + (long)((size_t)w * n_signers), rd.begin() + (long)((size_t)(w + 1) * n_signers));
+      x.trace = trace_flags && trace_flags[w];
+    }
+    const eddsa::SignResult r = eddsa::SignBatch(ws, tamper_wallet, tamper_kind);
+    for (uint32_t w = 0; w < count; ++w) {
+      std::memcpy(sigs + (size_t)w * 64, r.sig[w].data(), 64);
+      status[w] = r.status[w];
+    }
+    const size_t tw = (size_t)n_signers * eddsa::kTraceSignerWords + eddsa::kTraceDigestWords;
+    for (size_t t = 0; t < r.trace.size(); ++t) std::copy(r.trace[t].begin(), r.trace[t].end(), trace + t * tw);
+    if (gpu_s) *gpu_s = r.gpu_s;
   });
 }
 

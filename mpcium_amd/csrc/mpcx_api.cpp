@@ -69,6 +69,11 @@ hipError_t mpcx_launch_ec_msm(const uint32_t* a, const uint32_t* sc, const uint3
                               const uint32_t* gtab, uint32_t* ws, uint32_t count, uint32_t n_points, hipStream_t st);
 hipError_t mpcx_launch_ec_probe(uint32_t op, const uint32_t* a, const uint32_t* b, uint32_t* out, uint32_t count,
                                 hipStream_t st);
+hipError_t mpcx_launch_ed_msm(const uint32_t* a, const uint32_t* sc, const uint32_t* pts, uint32_t* out,
+                              const uint32_t* btab, uint32_t* ws, uint32_t count, uint32_t n_points, hipStream_t st);
+hipError_t mpcx_launch_ed_comb_entries(const uint32_t* in, uint32_t* out, uint32_t count, hipStream_t st);
+hipError_t mpcx_launch_ed_probe(uint32_t op, const uint32_t* a, const uint32_t* b, uint32_t* out, uint32_t count,
+                                hipStream_t st);
 }
 
 namespace {
@@ -231,6 +236,7 @@ struct Device {
   std::atomic<uint64_t> launches{0};  // kernel launches of the batch entry points on this device
   std::mutex ec_mu;            // guards the lazy secp256k1 base-point comb build
   uint32_t* ec_gtab = nullptr;  // d 256^w G, w < 32, 1 <= d <= 255 (affine x, y)
+  uint32_t* ed_btab = nullptr;  // Ed25519: d 256^w B, same order (y + x, y - x, 2 d x y)
 };
 Device g_devs[kMaxDevices];
 std::atomic<int> g_ndev{0};
@@ -1896,6 +1902,8 @@ int mpcx_shutdown(void) {
     drop_lane(d.build_lane);
     if (d.ec_gtab) (void)hipFree(d.ec_gtab);
     d.ec_gtab = nullptr;
+    if (d.ed_btab) (void)hipFree(d.ed_btab);
+    d.ed_btab = nullptr;
     {
       std::lock_guard<std::mutex> dl(d.dev_mu);
       for (auto& kv : d.dev_lanes) drop_lane(*kv.second);
@@ -2603,6 +2611,157 @@ int mpcx_ec_probe(uint32_t op, uint32_t count, const uint32_t* a, const uint32_t
   const hipError_t e = mpcx_launch_ec_probe(op, (const uint32_t*)l.stage[0].ptr, (const uint32_t*)l.stage[1].ptr,
                                             (uint32_t*)l.stage[2].ptr, count, l.st);
   if (e != hipSuccess) return hip_fail(e, "launch k_ec_probe");
+  return d2h_sync(out, l.stage[2].ptr, nb, l);
+}
+
+// ------------------------------------------------------------ Ed25519
+namespace {
+// the base point B of RFC 8032 (x, y)
+constexpr uint32_t kEdB[16] = {0x8F25D51Au, 0xC9562D60u, 0x9525A7B2u, 0x692CC760u, 0xFDD6DC5Cu, 0xC0A4E231u,
+                               0xCD6E53FEu, 0x216936D3u, 0x66666658u, 0x66666666u, 0x66666666u, 0x66666666u,
+                               0x66666666u, 0x66666666u, 0x66666666u, 0x66666666u};
+// k_ed_msm's per-thread tables: 15 entries of 32 words (Y + X, Y - X, 2 Z, 2 d T) per point, 64 lanes per block
+constexpr size_t kEdMsmPointBytes = 15u * 32u * 64u * 4u;
+
+// The Ed25519 base-point comb of device d, built on first use as ec_gtab is:
+// entry (w, v) = (v 2^(8w)) B as a plain scalar multiple of B by k_ed_msm
+// itself, then every affine result turned into its mixed-addition entry. The
+// caller holds lane l.
+int ed_btab(Device& d, Lane& l, const uint32_t** out) {
+  std::lock_guard<std::mutex> lk(d.ec_mu);
+  if (!d.ed_btab) {
+    std::vector<uint32_t> sc((size_t)kEcTabEntries * 8u, 0u), pts((size_t)kEcTabEntries * 16u, 0u);
+    for (uint32_t w = 0; w < 32; ++w)
+      for (uint32_t v = 1; v <= 255; ++v) {
+        const size_t e = (size_t)w * 255u + (v - 1u);
+        sc[e * 8u + w / 4u] = v << (8u * (w % 4u));
+        std::memcpy(&pts[e * 16u], kEdB, sizeof kEdB);
+      }
+    int rc;
+    const size_t sb = sc.size() * 4, pb = pts.size() * 4, ob = (size_t)kEcTabEntries * 16u * 4u;
+    if ((rc = ensure_buffer(l.stage[0], sb)) || (rc = ensure_buffer(l.stage[1], pb)) ||
+        (rc = ensure_buffer(l.stage[2], ob)) ||
+        (rc = ensure_workspace(l, (size_t)((kEcTabEntries + 63u) / 64u) * kEdMsmPointBytes)))
+      return rc;
+    uint32_t* tab = nullptr;
+    hipError_t e = hipMalloc((void**)&tab, (size_t)kEcTabEntries * 24u * 4u);
+    if (e != hipSuccess) return fail(MPCX_ENOMEM, "hipMalloc(Ed25519 comb): %s", hipGetErrorString(e));
+    if ((rc = h2d(l, l.stage[0].ptr, sc.data(), sb)) || (rc = h2d(l, l.stage[1].ptr, pts.data(), pb))) {
+      (void)hipFree(tab);
+      return rc;
+    }
+    e = mpcx_launch_ed_msm(nullptr, (const uint32_t*)l.stage[0].ptr, (const uint32_t*)l.stage[1].ptr,
+                           (uint32_t*)l.stage[2].ptr, nullptr, l.ws, kEcTabEntries, 1u, l.st);
+    if (e == hipSuccess)
+      e = mpcx_launch_ed_comb_entries((const uint32_t*)l.stage[2].ptr, tab, kEcTabEntries, l.st);
+    if (e != hipSuccess) {
+      (void)hipFree(tab);
+      return hip_fail(e, "launch k_ed_msm (comb build)");
+    }
+    if ((rc = lane_wait(l))) {
+      (void)hipFree(tab);
+      return rc;
+    }
+    d.ed_btab = tab;
+  }
+  *out = d.ed_btab;
+  return MPCX_OK;
+}
+
+int ed_msm_range(int di, uint32_t count, uint32_t n_points, const uint32_t* a, const uint32_t* scalars,
+                 const uint32_t* points, uint32_t* out) {
+  Device& d = g_devs[di];
+  std::unique_lock<std::mutex> lk;
+  Lane& l = acquire_lane(d, lk);
+  LaneDrain drain(l);
+  int rc;
+  if ((rc = lane_stream(l))) return rc;
+  const uint32_t* btab = nullptr;
+  if ((rc = ed_btab(d, l, &btab))) return rc;
+  // consecutive launches of at most per_launch blocks keep the tables under the cap; one block always runs
+  const size_t block_bytes = (size_t)n_points * kEdMsmPointBytes;
+  const uint32_t blocks = (count + 63u) / 64u;
+  const uint32_t per_launch =
+      block_bytes ? (uint32_t)std::min<size_t>(blocks, std::max<size_t>(1, ((size_t)g_ec_msm_ws_mb << 20) / block_bytes))
+                  : blocks;
+  const size_t ab = a ? (size_t)count * 8u * 4u : 0, sb = (size_t)count * n_points * 8u * 4u,
+               pb = (size_t)count * n_points * 16u * 4u, ob = (size_t)count * 16u * 4u;
+  if ((n_points && ((rc = ensure_buffer(l.stage[0], sb)) || (rc = ensure_buffer(l.stage[1], pb)) ||
+                    (rc = ensure_workspace(l, (size_t)per_launch * block_bytes)))) ||
+      (rc = ensure_buffer(l.stage[2], ob)) || (a && (rc = ensure_buffer(l.stage[3], ab))))
+    return rc;
+  if ((n_points && ((rc = h2d(l, l.stage[0].ptr, scalars, sb)) || (rc = h2d(l, l.stage[1].ptr, points, pb)))) ||
+      (a && (rc = h2d(l, l.stage[3].ptr, a, ab))))
+    return rc;
+  const uint32_t *d_sc = n_points ? (const uint32_t*)l.stage[0].ptr : nullptr,
+                 *d_pt = n_points ? (const uint32_t*)l.stage[1].ptr : nullptr,
+                 *d_a = a ? (const uint32_t*)l.stage[3].ptr : nullptr;
+  uint32_t* d_out = (uint32_t*)l.stage[2].ptr;
+  for (uint32_t b0 = 0; b0 < blocks; b0 += per_launch) {
+    const uint32_t first = b0 * 64u, n = std::min(count - first, per_launch * 64u);
+    const int ks = kstat_begin(l);
+    hipError_t e = mpcx_launch_ed_msm(d_a ? d_a + (size_t)first * 8u : nullptr,
+                                      d_sc ? d_sc + (size_t)first * n_points * 8u : nullptr,
+                                      d_pt ? d_pt + (size_t)first * n_points * 16u : nullptr,
+                                      d_out + (size_t)first * 16u, btab, n_points ? l.ws : nullptr, n, n_points, l.st);
+    if (e != hipSuccess) return hip_fail(e, "launch k_ed_msm");
+    kstat_end(l, ks, d, di, "ed_msm", -1, n, 0.0);
+    d.launches.fetch_add(1, std::memory_order_relaxed);
+    launch_log("ed_msm", -1, n, 256, 256, 0.0);
+  }
+  return d2h_sync(out, l.stage[2].ptr, ob, l);
+}
+
+// v (8 words) >= p = 2^255 - 19
+bool ed_geq_p(const uint32_t* v) {
+  if (v[7] >> 31) return true;
+  uint32_t hi = v[7] | 0x80000000u;
+  for (int i = 1; i < 7; ++i) hi &= v[i];
+  return hi == 0xFFFFFFFFu && v[0] >= 0xFFFFFFEDu;
+}
+}  // namespace
+
+int mpcx_ed_msm_batch(uint32_t count, uint32_t n_points, const uint32_t* a, const uint32_t* scalars,
+                      const uint32_t* points, uint32_t* out) {
+  if (n_points > MPCX_ED_MSM_MAX_POINTS)
+    return fail(MPCX_EINVAL, "n_points %u outside [0, %d]", n_points, MPCX_ED_MSM_MAX_POINTS);
+  if (n_points == 0 && !a) return fail(MPCX_EINVAL, "n_points 0 needs the base-point scalars a");
+  if (!out || (n_points && (!scalars || !points))) return fail(MPCX_EINVAL, "null buffer");
+  if (count == 0) return MPCX_OK;
+  return run_sliced(count, g_split_min, [&](int di, uint32_t first, uint32_t n) {
+    return ed_msm_range(di, n, n_points, a ? a + (size_t)first * 8u : nullptr,
+                        n_points ? scalars + (size_t)first * n_points * 8u : nullptr,
+                        n_points ? points + (size_t)first * n_points * 16u : nullptr, out + (size_t)first * 16u);
+  });
+}
+
+// One field or point operation of mpcx_ed_fe.hpp per item (k_ed_probe), on the
+// thread's selected device; for tests and tools.
+int mpcx_ed_probe(uint32_t op, uint32_t count, const uint32_t* a, const uint32_t* b, uint32_t* out) {
+  if (op > MPCX_ED_OP_ED_MADD) return fail(MPCX_EINVAL, "unknown Ed25519 probe op %u", op);
+  if (!a || !b || !out) return fail(MPCX_EINVAL, "null buffer");
+  if (count == 0) return MPCX_OK;
+  for (int s = 0; s < 2; ++s) {
+    const uint32_t* in = s ? b : a;
+    for (size_t e = 0; e < (size_t)count * 4u; ++e)
+      if (ed_geq_p(in + e * 8u))
+        return fail(MPCX_EINVAL, "item %zu: value %zu of input %c is >= p", e / 4u, e % 4u, s ? 'b' : 'a');
+  }
+  Device* dev = nullptr;
+  int rc;
+  if ((rc = selected(&dev))) return rc;
+  std::unique_lock<std::mutex> lk;
+  Lane& l = acquire_lane(*dev, lk);
+  LaneDrain drain(l);
+  if ((rc = lane_stream(l))) return rc;
+  const size_t nb = (size_t)count * 32u * 4u;
+  if ((rc = ensure_buffer(l.stage[0], nb)) || (rc = ensure_buffer(l.stage[1], nb)) ||
+      (rc = ensure_buffer(l.stage[2], nb)))
+    return rc;
+  if ((rc = h2d(l, l.stage[0].ptr, a, nb)) || (rc = h2d(l, l.stage[1].ptr, b, nb))) return rc;
+  const hipError_t e = mpcx_launch_ed_probe(op, (const uint32_t*)l.stage[0].ptr, (const uint32_t*)l.stage[1].ptr,
+                                            (uint32_t*)l.stage[2].ptr, count, l.st);
+  if (e != hipSuccess) return hip_fail(e, "launch k_ed_probe");
   return d2h_sync(out, l.stage[2].ptr, nb, l);
 }
 

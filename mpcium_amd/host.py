@@ -78,6 +78,11 @@ SIGNATURES = [
     ("mpcxh_vss_verify_batch", _i, [_u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp]),
     ("mpcxh_vss_public_shares_batch", _i, [_u32, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
     ("mpcxh_vss_reconstruct_batch", _i, [_u32, _u32, _vp, _u32, _vp, _vp, _vp]),
+    ("mpcxh_ed25519_decode_batch", _i, [_u32, _vp, _vp, _vp]),
+    ("mpcxh_ed25519_hram_batch", _i, [_u32, _vp, _vp, _vp, _vp, _vp]),
+    ("mpcxh_eddsa_verify_batch", _i, [_u32, _vp, _vp, _vp, _vp, _vp]),
+    ("mpcxh_eddsa_sign_batch", _i, [_u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, ctypes.c_int64, _i,
+                                    _vp, _vp, _vp, _vp]),
 ]
 
 ERR_OK, ERR_MESSAGE_TOO_LONG, ERR_MESSAGE_MALFORMED = 0, 1, 2

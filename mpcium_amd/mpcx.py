@@ -61,6 +61,8 @@ SIGNATURES = [
     ("mpcx_ec_combine_batch", ctypes.c_int, [ctypes.c_uint32, _vp, _vp, _vp]),
     ("mpcx_ec_msm_batch", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
     ("mpcx_ec_probe", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp]),
+    ("mpcx_ed_msm_batch", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
+    ("mpcx_ed_probe", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp]),
     ("mpcx_modexp_multi_batch", ctypes.c_int, [ctypes.c_uint32, _vp]),
     ("mpcx_mr_batch", ctypes.c_int, [ctypes.c_uint32, _vp, ctypes.c_uint32, _vp, _vp]),
     ("mpcx_fixedbase_register", ctypes.c_int, [_vp, _vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.POINTER(_vp)]),
@@ -602,6 +604,83 @@ def ec_probe(op: Union[str, int], a: Sequence, b: Optional[Sequence] = None) -> 
     if code <= EC_OPS["inv"]:
         return [v & mask for v in res]
     return [(v & mask, (v >> 256) & mask, v >> 512) for v in res]
+
+
+ED_MSM_MAX_POINTS = 16
+
+
+def ed_msm_batch(items) -> list:
+    """Ed25519 a B + sum_k b_k P_k per item (a, [(b_k, P_k), ...]), a an
+    integer or None (no item of the batch has a B term when every a is None),
+    points as affine (x, y) tuples or None (no term) -> list of (x, y); the
+    identity is (0, 1). Scalars are integers in [0, 2^256), used as they are
+    (not reduced mod the group order); items with fewer terms than the batch's
+    widest are padded with zero scalars and all-zero points. A batch whose
+    items all have no terms is the plain a B (n_points = 0)."""
+    n = len(items)
+    if n == 0:
+        return []
+    k = max(len(terms) for _, terms in items)
+    if k > ED_MSM_MAX_POINTS:
+        raise ValueError(f"an item has {k} terms > {ED_MSM_MAX_POINTS}")
+    with_a = any(a is not None for a, _ in items)
+    av = np.zeros((n, 8), dtype="<u4")
+    sc = np.zeros((n, max(k, 1) * 8), dtype="<u4")
+    pt = np.zeros((n, max(k, 1) * 16), dtype="<u4")
+    mask = (1 << 256) - 1
+    for i, (a, terms) in enumerate(items):
+        if a is not None:
+            if a < 0 or a >> 256:
+                raise ValueError("a scalar outside [0, 2^256)")
+            av[i] = int_to_words(a, 8)
+        s = p = 0
+        for j, (b, P) in enumerate(terms):
+            if b < 0 or b >> 256:
+                raise ValueError("a scalar outside [0, 2^256)")
+            s |= b << (256 * j)
+            if P is not None:
+                p |= (P[0] | (P[1] << 256)) << (512 * j)
+        sc[i] = int_to_words(s, max(k, 1) * 8)
+        pt[i] = int_to_words(p, max(k, 1) * 16)
+    out = np.zeros((n, 16), dtype="<u4")
+    _check(lib().mpcx_ed_msm_batch(n, k, av.ctypes.data if with_a else None, sc.ctypes.data, pt.ctypes.data,
+                                   out.ctypes.data))
+    return [(v & mask, v >> 256) for v in words_to_ints(out)]
+
+
+ED_OPS = {"add": 0, "sub": 1, "mul": 2, "sqr": 3, "inv": 4, "ed_dbl": 5, "ed_add": 6, "ed_madd": 7}
+
+
+def ed_probe(op: Union[str, int], a: Sequence, b: Optional[Sequence] = None) -> list:
+    """mpcx_ed_probe (for tests and tools): one field or point operation of the
+    Ed25519 kernel per item. An item of a / b is a field element (int) or a
+    tuple of up to four ints (X, Y, Z, T, or the entry y + x, y - x, 2 d x y of
+    ed_madd's b; missing ones are 0); b defaults to zeros. Field ops return
+    ints, point ops (X, Y, Z, T) tuples."""
+    code = ED_OPS[op] if isinstance(op, str) else int(op)
+    n = len(a)
+    if b is None:
+        b = [0] * n
+    if len(b) != n:
+        raise ValueError("length mismatch")
+
+    def pack(items):
+        vals = []
+        for it in items:
+            t = tuple(it) if isinstance(it, (tuple, list)) else (it,)
+            if len(t) > 4 or any(v < 0 or v >> 256 for v in t):
+                raise ValueError("a probe item is up to four values in [0, 2^256)")
+            vals.append(sum(int(v) << (256 * i) for i, v in enumerate(t)))
+        return ints_to_words(vals, 32) if n else np.zeros((1, 32), dtype="<u4")
+
+    A, B = pack(a), pack(b)
+    out = np.zeros((max(n, 1), 32), dtype="<u4")
+    _check(lib().mpcx_ed_probe(code, n, A.ctypes.data, B.ctypes.data, out.ctypes.data))
+    mask = (1 << 256) - 1
+    res = words_to_ints(out[:n])
+    if code <= ED_OPS["inv"]:
+        return [v & mask for v in res]
+    return [(v & mask, (v >> 256) & mask, (v >> 512) & mask, v >> 768) for v in res]
 
 
 def fermat2_batch(cands: Sequence[int]) -> List[bool]:

@@ -14,6 +14,14 @@ scalars below 2^B (1: every scalar 1, a sum of points), which is what the
 kernel's window skip is for.
 
     python tools/ec_bench.py --points 16 --sizes 2560,25600
+
+--curve ed25519 (with --points N) times k_ed_msm (Ed25519 a B + sum of N terms
+b P, mpcx_ed_msm_batch; full-width scalars below L, a B in every item) and, in
+the same run on the same box, k_ec_msm on secp256k1 items of the same shape.
+--sign-wallets W adds the wall time of one eddsa.sign_batch over W wallets at
+2 of 3 with its share spent inside the GPU batches.
+
+    python tools/ec_bench.py --curve ed25519 --points 16 --sizes 2560,25600 --sign-wallets 10000
 """
 import argparse
 import json
@@ -32,6 +40,9 @@ def main():
     ap.add_argument("--points", type=int, default=0, help="time ec_msm_batch at this many points per item")
     ap.add_argument("--scalar-bits", type=int, default=256,
                     help="with --points: draw the b scalars below 2^bits (1: sums of points; the window skip)")
+    ap.add_argument("--curve", choices=("secp256k1", "ed25519"), default="secp256k1")
+    ap.add_argument("--sign-wallets", type=int, default=0,
+                    help="with --curve ed25519: also time eddsa.sign_batch over this many wallets at 2 of 3")
     args = ap.parse_args()
     from mpcium_amd import mpcx
     from oracle import tss_ref as T
@@ -51,6 +62,10 @@ def main():
         k = [x for x in ks["kernels"] if x["kind"] == kind][0]
         return k["kernel_ms"] / args.reps, k["launches"] // args.reps
 
+    if args.curve == "ed25519":
+        ed25519_rows(args, mpcx, T, rng, pts, timed, out)
+        print(json.dumps(out))
+        return
     if args.points:
         np_ = args.points
         for size in (int(x) for x in args.sizes.split(",")):
@@ -105,6 +120,61 @@ def main():
             out["rows"].append(row)
             print(json.dumps(row), flush=True)
     print(json.dumps(out))
+
+
+def ed25519_rows(args, mpcx, T, rng, secp_pts, timed, out):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import time
+
+    import ed_model as M  # the integer model the tests use
+    ed_pts = [M.mul(rng.randrange(1, M.L), M.BASE) for _ in range(64)]
+    np_ = args.points
+    for size in (int(x) for x in args.sizes.split(",")) if np_ else ():
+        top = M.L if args.scalar_bits >= 256 else 1 << args.scalar_bits
+        shape = [(rng.randrange(M.L), [(rng.randrange(1, top), (i * 7 + 3 * k) % 64) for k in range(np_)])
+                 for i in range(size)]
+        ed_items = [(a, [(b, ed_pts[j]) for b, j in t]) for a, t in shape]
+        ec_items = [(a, [(b, secp_pts[j]) for b, j in t]) for a, t in shape]
+        got = mpcx.ed_msm_batch(ed_items)  # warm-up + check
+        for i in range(0, size, max(1, size // 6)):
+            assert got[i] == M.msm(*ed_items[i]), (size, np_, i)
+        mpcx.ec_msm_batch(ec_items)
+        for name, kind, fn, its in (("k_ed_msm", "ed_msm", mpcx.ed_msm_batch, ed_items),
+                                    ("k_ec_msm", "ec_msm", mpcx.ec_msm_batch, ec_items)):
+            ms, launches = timed(kind, fn, its)
+            row = {"items": size, "points": np_, "scalar_bits": args.scalar_bits, "kernel": name, "launches": launches,
+                   "kernel_ms": round(ms, 3), "items_per_s": round(size / ms * 1e3)}
+            out["rows"].append(row)
+            print(json.dumps(row), flush=True)
+    if args.sign_wallets:
+        from mpcium_amd import eddsa, host
+        host.init(0)
+        W, ids = args.sign_wallets, [1, 2, 3]
+        ws = []
+        for w in range(W):
+            x, c1 = rng.randrange(1, M.L), rng.randrange(1, M.L)
+            ws.append({"ids": ids[:2], "shares": [(x + c1 * i) % M.L for i in ids[:2]], "pk": None, "x": x,
+                       "msg": rng.randbytes(32), "session": rng.randbytes(32), "readers": [2 * w + 1, 2 * w + 2]})
+        pks = mpcx.ed_msm_batch([(w["x"], []) for w in ws])
+        for w, pk in zip(ws, pks):
+            w["pk"] = pk
+        eddsa.sign_batch(ws[:256])  # warm-up
+        mpcx.set_option("kernel_stats", 1)
+        mpcx.kernel_stats(reset=True)
+        t0 = time.perf_counter()
+        r = eddsa.sign_batch(ws)
+        wall = time.perf_counter() - t0
+        ks = mpcx.kernel_stats()
+        mpcx.set_option("kernel_stats", 0)
+        assert r["status"] == [0] * W
+        for i in range(0, W, max(1, W // 6)):
+            assert M.verify_point(ws[i]["pk"], ws[i]["msg"], r["sigs"][i]), i
+        k = [x for x in ks["kernels"] if x["kind"] == "ed_msm"][0]
+        row = {"sign_batch_wallets": W, "signers": 2, "wall_s": round(wall, 4), "gpu_batches_s": round(r["gpu_s"], 4),
+               "gpu_share": round(r["gpu_s"] / wall, 3), "kernel_ms": round(k["kernel_ms"], 3),
+               "launches": k["launches"], "signatures_per_s": round(W / wall)}
+        out["rows"].append(row)
+        print(json.dumps(row), flush=True)
 
 
 if __name__ == "__main__":

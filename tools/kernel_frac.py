@@ -23,6 +23,8 @@ def kname(kind, geom):
         return "k_ec_combine"
     if kind == "ec_msm":
         return "k_ec_msm"
+    if kind == "ed_msm":
+        return "k_ed_msm"
     P, K, G = GEOM[geom]
     return f"k_{kind}<{P}, {K}, {G},"
 
