@@ -298,6 +298,26 @@ int mpcx_ed_msm_batch(uint32_t count, uint32_t n_points,
                       const uint32_t* points,   /* count x n_points x 16 words (x, y); all-zero = no term */
                       uint32_t* out);           /* count x 16 words (x, y) */
 
+#define MPCX_ED_ADMIT_OK 0       /* accepted */
+#define MPCX_ED_ADMIT_RANGE 1    /* x >= p or y >= p */
+#define MPCX_ED_ADMIT_OFFCURVE 2 /* -x^2 + y^2 != 1 + d x^2 y^2; (0, 0) is one */
+/* Admission of received Ed25519 points, what tss-lib does to every commitment
+ * point of an EdDSA keygen or resharing round: crypto.NewECPoint's check, then
+ * (clear == 1) EightInvEight, P -> 8 (c P) with c = 8^-1 mod L, which is the
+ * order-L component of P: the identity map on a point of order L, and the
+ * identity and the eight small-order points come out as (0, 1). count
+ * independent items, one GPU thread each (k_ed_admit: the fixed addition chain
+ * of c's non-adjacent form, no table and no workspace). A point is x, y, 8
+ * little-endian words each, ANY 256-bit values: the kernel itself decides
+ * status[i] (MPCX_ED_ADMIT_*), and a bad point does not fail the call. A
+ * rejected item's output is all zero; with clear == 0 an accepted point comes
+ * back unchanged. The argument checks come before any device is touched: a
+ * null buffer or clear > 1 is MPCX_EINVAL; count == 0 is then MPCX_OK. */
+int mpcx_ed_admit_batch(uint32_t count, uint32_t clear,
+                        const uint32_t* points,  /* count x 16 words (x, y) */
+                        uint32_t* out,           /* count x 16 words (x, y); all-zero = rejected */
+                        uint8_t* status);        /* count */
+
 /* Miller-Rabin: ok[i] = n_i is a strong probable prime to base bases[i]
  * (5 <= n_i < 2^1024 odd, bases[i] < 2^(32*n_words); a base that is 0 mod
  * n_i reports "composite"). Each candidate is its own modulus. Serves

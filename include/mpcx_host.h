@@ -32,6 +32,12 @@
  *   mpcxh_eddsa_verify_batch     decred edwards/v2 Verify, called at
  *                                /root/reference/pkg/mpc/eddsa_signing_session.go
  *   mpcxh_eddsa_sign_batch       up:eddsa/signing round_1.go .. finalize.go
+ *   mpcxh_ed25519_admit_batch    up:crypto/ecpoint.go NewECPoint, EightInvEight
+ *   mpcxh_edvss_*_batch          up:crypto/vss/feldman_vss.go over Edwards
+ *   mpcxh_eddsa_keygen_batch     up:eddsa/keygen round_1.go .. round_3.go, called through
+ *                                /root/reference/pkg/mpc/eddsa_keygen_session.go
+ *   mpcxh_eddsa_reshare_batch    up:eddsa/resharing, called through
+ *                                /root/reference/pkg/mpc/eddsa_resharing_session.go
  */
 #ifndef MPCX_HOST_H_
 #define MPCX_HOST_H_
@@ -333,6 +339,87 @@ int mpcxh_eddsa_sign_batch(uint32_t count, uint32_t n_signers, const uint32_t* i
                            const uint8_t* trace_flags, int64_t tamper_wallet, int tamper_kind,
                            uint8_t* sigs /* count x 64 */, uint8_t* status /* count */, uint32_t* trace,
                            double* gpu_s);
+
+/* ---------------------------------------------------------------- EdDSA keygen and resharing
+ * The other two EdDSA sessions mpcium runs for every wallet
+ * (/root/reference/pkg/mpc/eddsa_keygen_session.go, eddsa_resharing_session.go
+ * over tss-lib v2 up:eddsa/keygen and up:eddsa/resharing): Feldman VSS over
+ * Ed25519 (csrc/host/edvss.hpp, the mirror of the secp256k1 entries above with
+ * scalars mod L and mpcx_ed_msm_batch for the sums; the identity is (0, 1),
+ * there is no all-zero point), the admission of received points, and the two
+ * protocols with every party replayed in process (csrc/host/eddsa_keygen.hpp
+ * gives the steps; restated as recalled: upstream, verify). Every entry but the
+ * reconstruction needs a bound device.
+ *
+ * What a receiver does to a commitment point before using it: crypto.NewECPoint's
+ * check, then (clear == 1) EightInvEight. mpcx_ed_admit_batch (k_ed_admit) with
+ * its statuses; a rejected item's output is all zero. clear > 1 is MPCX_EINVAL. */
+int mpcxh_ed25519_admit_batch(uint32_t count, uint32_t clear, const uint32_t* points /* count x 16 */,
+                              uint32_t* out /* count x 16 */, uint8_t* status /* count */);
+/* vss.Create over Ed25519: a_0 = secret mod L, a_1..a_t =
+ * GetRandomPositiveInt(readers[i], L); vs[i][k] = a_k B, shares[i][j] =
+ * sum_k a_k id_j^k mod L. Limits and errors as mpcxh_vss_create_batch, mod L. */
+int mpcxh_edvss_create_batch(uint32_t threshold, uint32_t n_ids, const uint32_t* ids, uint32_t id_words,
+                             uint32_t count, const uint32_t* secrets /* count x 8 */, const mpcxh_reader_t* readers,
+                             uint32_t* vs /* count x (t+1) x 16 */, uint32_t* shares /* count x n_ids x 8 */);
+/* (*Share).Verify: ok[i] = (L - share_i) B + sum_k id_i^k V_ik is the identity.
+ * ok[i] = 0 without failing the call when n_vs != t + 1, a V_ik has a coordinate
+ * >= p or is not on the curve, or id_i is 0 mod L. */
+int mpcxh_edvss_verify_batch(uint32_t threshold, uint32_t count, uint32_t n_vs,
+                             const uint32_t* vs /* count x n_vs x 16 */, const uint32_t* ids /* count x id_words */,
+                             uint32_t id_words, const uint32_t* shares /* count x 8 */, uint8_t* ok);
+/* vc[s][k] = sum_i vs[s][i][k] (vc[s][0] is the public key), xs[s][j] =
+ * sum_k id_j^k vc[s][k]. A point that is not on the curve is MPCX_EINVAL. */
+int mpcxh_edvss_public_shares_batch(uint32_t threshold, uint32_t n_parties, const uint32_t* ids, uint32_t id_words,
+                                    uint32_t count, const uint32_t* vs /* count x n_parties x (t+1) x 16 */,
+                                    uint32_t* vc /* count x (t+1) x 16 */, uint32_t* xs /* count x n_parties x 16 */);
+/* (Shares).ReConstruct mod L, on the host (no device needed); as
+ * mpcxh_vss_reconstruct_batch. */
+int mpcxh_edvss_reconstruct_batch(uint32_t count, uint32_t n_shares, const uint32_t* ids, uint32_t id_words,
+                                  const uint32_t* shares, uint32_t* secrets /* count x 8 */, uint8_t* ok);
+
+/* words per party of a traced keygen session: u_i (8), the commitment C_i (8),
+ * the proof's t (8) and alpha (16), V_i0..V_it as committed (16 each), the
+ * shares s_i0..s_i,n-1 as sent (8 each) */
+#define MPCXH_EDDSA_KEYGEN_TRACE_WORDS(t, n) (40u + 16u * ((t) + 1u) + 8u * (n))
+/* up:eddsa/keygen rounds 1-3 for `count` sessions of n_parties (2..16) parties
+ * at threshold t (1 <= t < n_parties) over the same ids (id_words 1..16 words
+ * each, used mod L; zero or equal ids are MPCX_EINVAL): session bytes
+ * (session_len each; party i proves under session || big.Int(i).Bytes()) and
+ * one reader per party. status[s] = 0 with pk[s], x[s][j] (party j's share)
+ * and X[s][j] = x_j B, or 3 (round 3) with culprit[s] the dealer whose
+ * decommitment, points, Schnorr proof or shares failed and the outputs zero;
+ * culprit is 255 otherwise. The other sessions are unaffected. trace_flags (or
+ * NULL) marks sessions to trace; trace receives, per flagged session in order,
+ * n_parties x MPCXH_EDDSA_KEYGEN_TRACE_WORDS(t, n_parties) words. Test hooks on
+ * dealer 0 of session tamper_session (-1 / 0 for none): 1 shifts its Schnorr
+ * response, 2 swaps two coordinates of its decommitment, 3 shifts the share
+ * s_01, 4 adds the point (sqrt(-1), 0) of order four to V_01 before committing
+ * (admission clears it: the session succeeds with the untampered result), 5
+ * commits to an off-curve V_01. gpu_s (or NULL) receives the wall time inside the GPU
+ * batches. */
+int mpcxh_eddsa_keygen_batch(uint32_t count, uint32_t threshold, uint32_t n_parties,
+                             const uint32_t* ids /* n_parties x id_words */, uint32_t id_words,
+                             const uint8_t* sessions /* count x session_len */, uint32_t session_len,
+                             const mpcxh_reader_t* readers /* count x n_parties */, const uint8_t* trace_flags,
+                             int64_t tamper_session, int tamper_kind, uint8_t* status /* count */,
+                             uint8_t* culprit /* count */, uint32_t* pk /* count x 16 */,
+                             uint32_t* x /* count x n_parties x 8 */, uint32_t* X /* count x n_parties x 16 */,
+                             uint32_t* trace, double* gpu_s);
+/* up:eddsa/resharing for `count` wallets: the n_old old parties of old_ids (at
+ * least the old threshold + 1 of them), their shares and the wallet's public
+ * key, one reader per old party, to the n_new parties of new_ids at
+ * new_threshold (1 <= new_threshold < n_new <= 16). status[s] = 0 with
+ * pk_out[s] == pk[s], the new shares x[s][j] and X[s][j], or 4 with the
+ * outputs zero: culprit[s] is the old party whose decommitment, points or
+ * shares failed, or 255 when the dealt constant terms do not sum to pk[s]. */
+int mpcxh_eddsa_reshare_batch(uint32_t count, uint32_t n_old, const uint32_t* old_ids /* n_old x old_id_words */,
+                              uint32_t old_id_words, const uint32_t* shares /* count x n_old x 8 */,
+                              const uint32_t* pk /* count x 16 */, const mpcxh_reader_t* readers /* count x n_old */,
+                              uint32_t new_threshold, uint32_t n_new, const uint32_t* new_ids /* n_new x new_id_words */,
+                              uint32_t new_id_words, uint8_t* status /* count */, uint8_t* culprit /* count */,
+                              uint32_t* pk_out /* count x 16 */, uint32_t* x /* count x n_new x 8 */,
+                              uint32_t* X /* count x n_new x 16 */, double* gpu_s);
 
 /* Config-4 driver: one GG18 signature for each of `wallets` wallets, signed by
  * the first `signers` of `n_nodes` nodes (keys: Paillier private keys + own

@@ -21,12 +21,12 @@ HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result"]
 KERNEL_HDRS = ["mpcx_device.hpp", "mpcx_mx.hpp", "mpcx_internal.h"]
 # headers only some translation units include: the secp256k1 field and point
 # arithmetic shared by k_ec_combine, k_ec_msm and the test probe, and the
-# Ed25519 one shared by k_ed_msm and its probe
+# Ed25519 one shared by k_ed_msm, k_ed_admit and the probe
 SOURCE_HDRS = {"mpcx_ec.hip": ["mpcx_ec_fe.hpp"], "mpcx_ec_msm.hip": ["mpcx_ec_fe.hpp"],
                "mpcx_ec_probe.hip": ["mpcx_ec_fe.hpp"], "mpcx_ed_msm.hip": ["mpcx_ed_fe.hpp"],
-               "mpcx_ed_probe.hip": ["mpcx_ed_fe.hpp"]}
+               "mpcx_ed_probe.hip": ["mpcx_ed_fe.hpp"], "mpcx_ed_admit.hip": ["mpcx_ed_fe.hpp"]}
 HOST_SRCS = ["host/bignum.cpp", "host/engine.cpp", "host/modint.cpp", "host/paillier.cpp", "host/safeprime.cpp",
-             "host/tsscommon.cpp", "host/secp256k1.cpp", "host/mta.cpp", "host/proofs.cpp", "host/vss.cpp", "host/ed25519.cpp", "host/eddsa.cpp", "host/signing.cpp", "host/keygenload.cpp",
+             "host/tsscommon.cpp", "host/secp256k1.cpp", "host/mta.cpp", "host/proofs.cpp", "host/vss.cpp", "host/ed25519.cpp", "host/eddsa.cpp", "host/edvss.cpp", "host/eddsa_keygen.cpp", "host/signing.cpp", "host/keygenload.cpp",
              "host/hostprof.cpp", "host/gorand.cpp", "host/capi.cpp"]
 
 
@@ -46,7 +46,8 @@ def _objects():
     """(object, source, extra flags) of libmpcx.so: one k_modexp geometry per
     object (compiled in parallel: the unrolled Montgomery loops make each
     geometry ~30-60 s of hipcc), the prime kernels, the two secp256k1 kernels and
-    their test probe, the Ed25519 kernel and its probe, and the C-ABI host code."""
+    their test probe, the two Ed25519 kernels (k_ed_admit leaves the header's
+    table additions unused) and their probe, and the C-ABI host code."""
     objdir = os.path.join(HERE, "build")
     objs = [(os.path.join(objdir, f"mpcx_geom{g}.o"), "mpcx_geom.hip", [f"-DMPCX_GEOM_ID={g}"])
             for g in range(NUM_GEOMS)]
@@ -55,6 +56,7 @@ def _objects():
     objs.append((os.path.join(objdir, "mpcx_ec_msm.o"), "mpcx_ec_msm.hip", []))
     objs.append((os.path.join(objdir, "mpcx_ec_probe.o"), "mpcx_ec_probe.hip", []))
     objs.append((os.path.join(objdir, "mpcx_ed_msm.o"), "mpcx_ed_msm.hip", []))
+    objs.append((os.path.join(objdir, "mpcx_ed_admit.o"), "mpcx_ed_admit.hip", ["-Wno-unused-function"]))
     objs.append((os.path.join(objdir, "mpcx_ed_probe.o"), "mpcx_ed_probe.hip", []))
     objs.append((os.path.join(objdir, "mpcx_api.o"), "mpcx_api.cpp", []))
     return objs

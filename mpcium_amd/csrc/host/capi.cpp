@@ -24,6 +24,8 @@
 #include "signing.hpp"
 #include "vss.hpp"
 #include "eddsa.hpp"
+#include "eddsa_keygen.hpp"
+#include "edvss.hpp"
 
 using namespace mpcx::host;
 
@@ -822,6 +824,207 @@ int mpcxh_eddsa_sign_batch(uint32_t count, uint32_t n_signers, const uint32_t* i
     }
     const size_t tw = (size_t)n_signers * eddsa::kTraceSignerWords + eddsa::kTraceDigestWords;
     for (size_t t = 0; t < r.trace.size(); ++t) std::copy(r.trace[t].begin(), r.trace[t].end(), trace + t * tw);
+    if (gpu_s) *gpu_s = r.gpu_s;
+  });
+}
+
+// ---------------------------------------------------------------- EdDSA keygen and resharing
+static void ed_point_out(const ed::Point& P, uint32_t* out16) {
+  P.x.to_words(out16, 8);
+  P.y.to_words(out16 + 8, 8);
+}
+static void check_edvss_args(uint32_t threshold, uint32_t n_ids, uint32_t id_words) {
+  if (threshold >= edvss::kMaxTerms) throw std::invalid_argument("edvss: threshold + 1 > 16");
+  if (n_ids < 1 || n_ids > edvss::kMaxTerms) throw std::invalid_argument("edvss: 1..16 ids per call");
+  if (id_words < 1 || id_words > 16) throw std::invalid_argument("edvss: id_words outside [1, 16]");
+}
+
+int mpcxh_ed25519_admit_batch(uint32_t count, uint32_t clear, const uint32_t* points, uint32_t* out, uint8_t* status) {
+  return guard([&] {
+    if (clear > 1) throw std::invalid_argument("clear is not 0 or 1");
+    if (count && (!points || !out || !status)) throw std::invalid_argument("null buffer");
+    std::vector<ed::Point> in(count);
+    for (uint32_t i = 0; i < count; ++i) in[i] = ed_point_in(points + (size_t)i * 16);
+    const edvss::Admitted r = edvss::AdmitBatch(in, clear == 1);
+    for (uint32_t i = 0; i < count; ++i) {
+      status[i] = r.status[i];
+      if (r.status[i])
+        std::fill(out + (size_t)i * 16, out + (size_t)(i + 1) * 16, 0u);
+      else
+        ed_point_out(r.out[i], out + (size_t)i * 16);
+    }
+  });
+}
+
+int mpcxh_edvss_create_batch(uint32_t threshold, uint32_t n_ids, const uint32_t* ids, uint32_t id_words,
+                             uint32_t count, const uint32_t* secrets, const mpcxh_reader_t* rdr, uint32_t* vs,
+                             uint32_t* shares) {
+  return guard([&] {
+    check_edvss_args(threshold, n_ids, id_words);
+    if (threshold >= n_ids) throw std::invalid_argument("edvss: threshold >= number of ids");
+    if (!ids || (count && (!secrets || !rdr || !vs || !shares))) throw std::invalid_argument("null buffer");
+    std::vector<CounterDRBG> drbgs;
+    const auto rd = readers(rdr, count, &drbgs);
+    const auto out = edvss::CreateBatch(threshold, nats(ids, id_words, n_ids), nats(secrets, 8, count), rd);
+    for (uint32_t s = 0; s < count; ++s) {
+      for (uint32_t k = 0; k <= threshold; ++k) ed_point_out(out[s].Vs[k], vs + ((size_t)s * (threshold + 1) + k) * 16);
+      for (uint32_t j = 0; j < n_ids; ++j) out[s].shares[j].to_words(shares + ((size_t)s * n_ids + j) * 8, 8);
+    }
+  });
+}
+
+int mpcxh_edvss_verify_batch(uint32_t threshold, uint32_t count, uint32_t n_vs, const uint32_t* vs,
+                             const uint32_t* ids, uint32_t id_words, const uint32_t* shares, uint8_t* ok) {
+  return guard([&] {
+    check_edvss_args(threshold, 1, id_words);
+    if (n_vs > edvss::kMaxTerms) throw std::invalid_argument("edvss: n_vs > 16");
+    if (count && ((n_vs && !vs) || !ids || !shares || !ok)) throw std::invalid_argument("null buffer");
+    std::vector<edvss::VerifyItem> items(count);
+    for (uint32_t i = 0; i < count; ++i) {
+      items[i].Vs.resize(n_vs);
+      for (uint32_t k = 0; k < n_vs; ++k) items[i].Vs[k] = ed_point_in(vs + ((size_t)i * n_vs + k) * 16);
+      items[i].id = Nat::from_words(ids + (size_t)i * id_words, id_words);
+      items[i].share = Nat::from_words(shares + (size_t)i * 8, 8);
+    }
+    const auto r = edvss::VerifyBatch(threshold, items);
+    std::copy(r.begin(), r.end(), ok);
+  });
+}
+
+int mpcxh_edvss_public_shares_batch(uint32_t threshold, uint32_t n_parties, const uint32_t* ids, uint32_t id_words,
+                                    uint32_t count, const uint32_t* vs, uint32_t* vc, uint32_t* xs) {
+  return guard([&] {
+    check_edvss_args(threshold, n_parties, id_words);
+    if (!ids || (count && (!vs || !vc || !xs))) throw std::invalid_argument("null buffer");
+    const uint32_t t1 = threshold + 1;
+    std::vector<std::vector<std::vector<ed::Point>>> V(count);
+    for (uint32_t s = 0; s < count; ++s) {
+      V[s].assign(n_parties, std::vector<ed::Point>(t1));
+      for (uint32_t i = 0; i < n_parties; ++i)
+        for (uint32_t k = 0; k < t1; ++k) {
+          V[s][i][k] = ed_point_in(vs + (((size_t)s * n_parties + i) * t1 + k) * 16);
+          if (!ed::IsOnCurve(V[s][i][k])) throw std::invalid_argument("edvss: a commitment point is not on the curve");
+        }
+    }
+    const auto out = edvss::PublicSharesBatch(threshold, nats(ids, id_words, n_parties), V);
+    for (uint32_t s = 0; s < count; ++s) {
+      for (uint32_t k = 0; k < t1; ++k) ed_point_out(out[s].Vc[k], vc + ((size_t)s * t1 + k) * 16);
+      for (uint32_t j = 0; j < n_parties; ++j) ed_point_out(out[s].X[j], xs + ((size_t)s * n_parties + j) * 16);
+    }
+  });
+}
+
+int mpcxh_edvss_reconstruct_batch(uint32_t count, uint32_t n_shares, const uint32_t* ids, uint32_t id_words,
+                                  const uint32_t* shares, uint32_t* secrets, uint8_t* ok) {
+  return guard([&] {
+    check_edvss_args(0, n_shares, id_words);
+    if (count && (!ids || !shares || !secrets || !ok)) throw std::invalid_argument("null buffer");
+    std::vector<std::vector<Nat>> I(count), S(count);
+    for (uint32_t i = 0; i < count; ++i) {
+      I[i] = nats(ids + (size_t)i * n_shares * id_words, id_words, n_shares);
+      S[i] = nats(shares + (size_t)i * n_shares * 8, 8, n_shares);
+    }
+    const auto r = edvss::ReconstructBatch(I, S);
+    for (uint32_t i = 0; i < count; ++i) {
+      r[i].secret.to_words(secrets + (size_t)i * 8, 8);
+      ok[i] = r[i].ok ? 1 : 0;
+    }
+  });
+}
+
+// status, culprit, pk, x_j and X_j of every session (zero where aborted)
+static void keygen_out(const eddsa::KeygenResult& r, uint32_t count, uint32_t n, uint8_t* status, uint8_t* culprit,
+                       uint32_t* pk, uint32_t* x, uint32_t* X) {
+  std::fill(pk, pk + (size_t)count * 16, 0u);
+  std::fill(x, x + (size_t)count * n * 8, 0u);
+  std::fill(X, X + (size_t)count * n * 16, 0u);
+  for (uint32_t s = 0; s < count; ++s) {
+    status[s] = r.status[s];
+    culprit[s] = r.culprit[s];
+    if (r.status[s]) continue;
+    ed_point_out(r.pk[s], pk + (size_t)s * 16);
+    for (uint32_t j = 0; j < n; ++j) {
+      r.x[s][j].to_words(x + ((size_t)s * n + j) * 8, 8);
+      ed_point_out(r.X[s][j], X + ((size_t)s * n + j) * 16);
+    }
+  }
+}
+
+int mpcxh_eddsa_keygen_batch(uint32_t count, uint32_t threshold, uint32_t n_parties, const uint32_t* ids,
+                             uint32_t id_words, const uint8_t* sessions, uint32_t session_len,
+                             const mpcxh_reader_t* rdr, const uint8_t* trace_flags, int64_t tamper_session,
+                             int tamper_kind, uint8_t* status, uint8_t* culprit, uint32_t* pk, uint32_t* x,
+                             uint32_t* X, uint32_t* trace, double* gpu_s) {
+  return guard([&] {
+    if (n_parties < 2 || n_parties > edvss::kMaxTerms) throw std::invalid_argument("eddsa keygen: 2..16 parties");
+    if (threshold < 1 || threshold >= n_parties) throw std::invalid_argument("eddsa keygen: 1 <= threshold < parties");
+    if (id_words < 1 || id_words > 16) throw std::invalid_argument("eddsa keygen: id_words outside [1, 16]");
+    if (tamper_kind < 0 || tamper_kind > eddsa::kTamperKgOffCurve)
+      throw std::invalid_argument("eddsa keygen: unknown tamper kind");
+    if (!ids || (count && (!rdr || !status || !culprit || !pk || !x || !X || (session_len && !sessions))))
+      throw std::invalid_argument("null buffer");
+    if (gpu_s) *gpu_s = 0;
+    const std::vector<Nat> idv = edvss::CheckIndexes(nats(ids, id_words, n_parties));
+    if (!count) return;
+    size_t traced = 0;
+    for (uint32_t s = 0; trace_flags && s < count; ++s) traced += trace_flags[s] ? 1 : 0;
+    if (traced && !trace) throw std::invalid_argument("null trace buffer");
+    std::vector<CounterDRBG> drbgs;
+    const auto rd = readers(rdr, count * n_parties, &drbgs);
+    std::vector<eddsa::KeygenSession> ss(count);
+    for (uint32_t s = 0; s < count; ++s) {
+      if (session_len) ss[s].session.assign(sessions + (size_t)s * session_len, sessions + (size_t)(s + 1) * session_len);
+      ss[s].readers.assign(rd.begin() + (long)((size_t)s * n_parties), rd.begin() + (long)((size_t)(s + 1) * n_parties));
+      ss[s].trace = trace_flags && trace_flags[s];
+    }
+    const eddsa::KeygenResult r =
+        eddsa::KeygenBatch(ss, threshold, nats(ids, id_words, n_parties), tamper_session, tamper_kind);
+    keygen_out(r, count, n_parties, status, culprit, pk, x, X);
+    const size_t pw = MPCXH_EDDSA_KEYGEN_TRACE_WORDS(threshold, n_parties);
+    for (size_t q = 0; q < r.trace.size(); ++q)
+      for (uint32_t i = 0; i < n_parties; ++i) {
+        const eddsa::KeygenParty& p = r.trace[q][i];
+        uint32_t* o = trace + (q * n_parties + i) * pw;
+        p.u.to_words(o, 8);
+        p.C.to_words(o + 8, 8);
+        p.t.to_words(o + 16, 8);
+        ed_point_out(p.alpha, o + 24);
+        for (uint32_t k = 0; k <= threshold; ++k) ed_point_out(p.V[k], o + 40 + 16 * k);
+        for (uint32_t j = 0; j < n_parties; ++j) p.shares[j].to_words(o + 40 + 16 * (threshold + 1) + 8 * j, 8);
+      }
+    if (gpu_s) *gpu_s = r.gpu_s;
+  });
+}
+
+int mpcxh_eddsa_reshare_batch(uint32_t count, uint32_t n_old, const uint32_t* old_ids, uint32_t old_id_words,
+                              const uint32_t* shares, const uint32_t* pk, const mpcxh_reader_t* rdr,
+                              uint32_t new_threshold, uint32_t n_new, const uint32_t* new_ids, uint32_t new_id_words,
+                              uint8_t* status, uint8_t* culprit, uint32_t* pk_out, uint32_t* x, uint32_t* X,
+                              double* gpu_s) {
+  return guard([&] {
+    if (n_old < 1 || n_old > edvss::kMaxTerms) throw std::invalid_argument("eddsa reshare: 1..16 old parties");
+    if (n_new < 2 || n_new > edvss::kMaxTerms) throw std::invalid_argument("eddsa reshare: 2..16 new parties");
+    if (new_threshold < 1 || new_threshold >= n_new)
+      throw std::invalid_argument("eddsa reshare: 1 <= threshold < new parties");
+    if (old_id_words < 1 || old_id_words > 16 || new_id_words < 1 || new_id_words > 16)
+      throw std::invalid_argument("eddsa reshare: id_words outside [1, 16]");
+    if (!old_ids || !new_ids || (count && (!shares || !pk || !rdr || !status || !culprit || !pk_out || !x || !X)))
+      throw std::invalid_argument("null buffer");
+    if (gpu_s) *gpu_s = 0;
+    const std::vector<Nat> oi = nats(old_ids, old_id_words, n_old), ni = nats(new_ids, new_id_words, n_new);
+    edvss::CheckIndexes(oi);
+    edvss::CheckIndexes(ni);
+    if (!count) return;
+    std::vector<CounterDRBG> drbgs;
+    const auto rd = readers(rdr, count * n_old, &drbgs);
+    std::vector<eddsa::ReshareSession> ss(count);
+    for (uint32_t s = 0; s < count; ++s) {
+      ss[s].shares = nats(shares + (size_t)s * n_old * 8, 8, n_old);
+      ss[s].pk = ed_point_in(pk + (size_t)s * 16);
+      ss[s].readers.assign(rd.begin() + (long)((size_t)s * n_old), rd.begin() + (long)((size_t)(s + 1) * n_old));
+    }
+    const eddsa::KeygenResult r = eddsa::ReshareBatch(ss, oi, new_threshold, ni);
+    keygen_out(r, count, n_new, status, culprit, pk_out, x, X);
     if (gpu_s) *gpu_s = r.gpu_s;
   });
 }

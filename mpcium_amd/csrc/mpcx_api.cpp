@@ -74,6 +74,8 @@ hipError_t mpcx_launch_ed_msm(const uint32_t* a, const uint32_t* sc, const uint3
 hipError_t mpcx_launch_ed_comb_entries(const uint32_t* in, uint32_t* out, uint32_t count, hipStream_t st);
 hipError_t mpcx_launch_ed_probe(uint32_t op, const uint32_t* a, const uint32_t* b, uint32_t* out, uint32_t count,
                                 hipStream_t st);
+hipError_t mpcx_launch_ed_admit(const uint32_t* pts, uint32_t* out, uint8_t* status, uint32_t count, uint32_t clear,
+                                hipStream_t st);
 }
 
 namespace {
@@ -2732,6 +2734,40 @@ int mpcx_ed_msm_batch(uint32_t count, uint32_t n_points, const uint32_t* a, cons
     return ed_msm_range(di, n, n_points, a ? a + (size_t)first * 8u : nullptr,
                         n_points ? scalars + (size_t)first * n_points * 8u : nullptr,
                         n_points ? points + (size_t)first * n_points * 16u : nullptr, out + (size_t)first * 16u);
+  });
+}
+
+namespace {
+int ed_admit_range(int di, uint32_t count, uint32_t clear, const uint32_t* points, uint32_t* out, uint8_t* status) {
+  Device& d = g_devs[di];
+  std::unique_lock<std::mutex> lk;
+  Lane& l = acquire_lane(d, lk);
+  LaneDrain drain(l);
+  int rc;
+  if ((rc = lane_stream(l))) return rc;
+  const size_t pb = (size_t)count * 16u * 4u;
+  if ((rc = ensure_buffer(l.stage[0], pb)) || (rc = ensure_buffer(l.stage[2], pb)) ||
+      (rc = ensure_buffer(l.stage[3], count)))
+    return rc;
+  if ((rc = h2d(l, l.stage[0].ptr, points, pb))) return rc;
+  const int ks = kstat_begin(l);
+  const hipError_t e = mpcx_launch_ed_admit((const uint32_t*)l.stage[0].ptr, (uint32_t*)l.stage[2].ptr,
+                                            (uint8_t*)l.stage[3].ptr, count, clear, l.st);
+  if (e != hipSuccess) return hip_fail(e, "launch k_ed_admit");
+  kstat_end(l, ks, d, di, "ed_admit", -1, count, 0.0);
+  d.launches.fetch_add(1, std::memory_order_relaxed);
+  launch_log("ed_admit", -1, count, 256, 256, 0.0);
+  if ((rc = d2h(l, status, l.stage[3].ptr, count))) return rc;
+  return d2h_sync(out, l.stage[2].ptr, pb, l);
+}
+}  // namespace
+
+int mpcx_ed_admit_batch(uint32_t count, uint32_t clear, const uint32_t* points, uint32_t* out, uint8_t* status) {
+  if (clear > 1) return fail(MPCX_EINVAL, "clear %u is not 0 or 1", clear);
+  if (!points || !out || !status) return fail(MPCX_EINVAL, "null buffer");
+  if (count == 0) return MPCX_OK;
+  return run_sliced(count, g_split_min, [&](int di, uint32_t first, uint32_t n) {
+    return ed_admit_range(di, n, clear, points + (size_t)first * 16u, out + (size_t)first * 16u, status + first);
   });
 }
 

@@ -1,7 +1,7 @@
 // mpcx_ed_fe.hpp -- Ed25519 field and point arithmetic of the Edwards kernels
-// (device code): k_ed_msm (mpcx_ed_msm.hip) and the test probe k_ed_probe
-// (mpcx_ed_probe.hip) include the same text, so what the probe checks is what
-// the multi-scalar kernel runs.
+// (device code): k_ed_msm (mpcx_ed_msm.hip), k_ed_admit (mpcx_ed_admit.hip)
+// and the test probe k_ed_probe (mpcx_ed_probe.hip) include the same text, so
+// what the probe checks is what the kernels run.
 //
 // Field: p = 2^255 - 19, eight 32-bit limbs, values kept < p (the contract of
 // mpcx_ec_fe.hpp); a product is folded with 2^256 = 38 and bit 255 with

@@ -83,6 +83,15 @@ SIGNATURES = [
     ("mpcxh_eddsa_verify_batch", _i, [_u32, _vp, _vp, _vp, _vp, _vp]),
     ("mpcxh_eddsa_sign_batch", _i, [_u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, ctypes.c_int64, _i,
                                     _vp, _vp, _vp, _vp]),
+    ("mpcxh_ed25519_admit_batch", _i, [_u32, _u32, _vp, _vp, _vp]),
+    ("mpcxh_edvss_create_batch", _i, [_u32, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp]),
+    ("mpcxh_edvss_verify_batch", _i, [_u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp]),
+    ("mpcxh_edvss_public_shares_batch", _i, [_u32, _u32, _vp, _u32, _u32, _vp, _vp, _vp]),
+    ("mpcxh_edvss_reconstruct_batch", _i, [_u32, _u32, _vp, _u32, _vp, _vp, _vp]),
+    ("mpcxh_eddsa_keygen_batch", _i, [_u32, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, ctypes.c_int64, _i, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp]),
+    ("mpcxh_eddsa_reshare_batch", _i, [_u32, _u32, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp,
+                                       _vp, _vp]),
 ]
 
 ERR_OK, ERR_MESSAGE_TOO_LONG, ERR_MESSAGE_MALFORMED = 0, 1, 2

@@ -62,6 +62,7 @@ SIGNATURES = [
     ("mpcx_ec_msm_batch", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
     ("mpcx_ec_probe", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp]),
     ("mpcx_ed_msm_batch", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp, _vp]),
+    ("mpcx_ed_admit_batch", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp]),
     ("mpcx_ed_probe", ctypes.c_int, [ctypes.c_uint32, ctypes.c_uint32, _vp, _vp, _vp]),
     ("mpcx_modexp_multi_batch", ctypes.c_int, [ctypes.c_uint32, _vp]),
     ("mpcx_mr_batch", ctypes.c_int, [ctypes.c_uint32, _vp, ctypes.c_uint32, _vp, _vp]),
@@ -646,6 +647,26 @@ def ed_msm_batch(items) -> list:
     _check(lib().mpcx_ed_msm_batch(n, k, av.ctypes.data if with_a else None, sc.ctypes.data, pt.ctypes.data,
                                    out.ctypes.data))
     return [(v & mask, v >> 256) for v in words_to_ints(out)]
+
+
+def ed_admit_batch(points, clear: bool = True):
+    """mpcx_ed_admit_batch: crypto.NewECPoint's check and (clear) EightInvEight
+    per received Ed25519 point. points: (x, y) tuples of any integers in
+    [0, 2^256) -> (out, status): out[i] the admitted point, the order-L component
+    of points[i] when clear, or None when rejected; status[i] 0, 1 (a coordinate
+    >= p) or 2 (not on the curve)."""
+    n = len(points)
+    if n == 0:
+        return [], []
+    if any(v < 0 or v >> 256 for Q in points for v in Q):
+        raise ValueError("a coordinate outside [0, 2^256)")
+    pt = ints_to_words([x | (y << 256) for x, y in points], 16)
+    out = np.zeros((n, 16), dtype="<u4")
+    st = np.zeros(n, dtype=np.uint8)
+    _check(lib().mpcx_ed_admit_batch(n, 1 if clear else 0, pt.ctypes.data, out.ctypes.data, st.ctypes.data))
+    mask = (1 << 256) - 1
+    status = [int(v) for v in st]
+    return [None if s else (v & mask, v >> 256) for v, s in zip(words_to_ints(out), status)], status
 
 
 ED_OPS = {"add": 0, "sub": 1, "mul": 2, "sqr": 3, "inv": 4, "ed_dbl": 5, "ed_add": 6, "ed_madd": 7}

@@ -105,3 +105,76 @@ def reconstruct_batch(items: Sequence[Sequence[tuple]]) -> List[Optional[int]]:
     _host._check(_host.lib().mpcxh_vss_reconstruct_batch(m, k, I.ctypes.data, iw, S.ctypes.data, out.ctypes.data,
                                                          ok.ctypes.data))
     return [v if o else None for v, o in zip(words_to_ints(out), ok)]
+
+
+# ------------------------------------------------------------ Feldman VSS over Ed25519
+# The same four calls with scalars mod L and the point sums on k_ed_msm
+# (include/mpcx_host.h "EdDSA keygen and resharing"; C++ in csrc/host/edvss.cpp),
+# for tss-lib's eddsa/keygen and eddsa/resharing. Points are (x, y) tuples; the
+# identity is (0, 1) and there is no None.
+def _ed_points_out(a: np.ndarray) -> list:
+    return [(v & _MASK, v >> 256) for v in words_to_ints(a.reshape(-1, 16))]
+
+
+def edvss_create_batch(threshold: int, ids: Sequence[int], secrets: Sequence[int], readers) -> List[tuple]:
+    """vss.Create over Ed25519 per secret -> [(Vs, shares)] as create_batch."""
+    n, m = len(ids), len(secrets)
+    if len(readers) != m:
+        raise ValueError("one reader per secret")
+    I, iw = _ids(ids)
+    S = np.ascontiguousarray(ints_to_words(list(secrets), 8)) if m else np.zeros((1, 8), dtype="<u4")
+    R = _host.Readers(readers)
+    t1 = threshold + 1
+    vs = np.zeros((max(m, 1), max(t1, 1) * 16), dtype="<u4")
+    sh = np.zeros((max(m, 1), max(n, 1) * 8), dtype="<u4")
+    _host._check(_host.lib().mpcxh_edvss_create_batch(threshold, n, I.ctypes.data, iw, m, S.ctypes.data, R.ptr,
+                                                      vs.ctypes.data, sh.ctypes.data))
+    return [(_ed_points_out(vs[s]), words_to_ints(sh[s].reshape(n, 8))) for s in range(m)]
+
+
+def edvss_verify_batch(threshold: int, items: Sequence[tuple]) -> List[bool]:
+    """(*Share).Verify over Ed25519 per item (Vs, id, share), as verify_batch."""
+    m = len(items)
+    if m == 0:
+        return []
+    n_vs = len(items[0][0])
+    if any(len(it[0]) != n_vs for it in items):
+        raise ValueError("items must carry the same number of commitment points")
+    V = _points_in([P for it in items for P in it[0]])
+    I, iw = _ids([it[1] for it in items])
+    S = np.ascontiguousarray(ints_to_words([it[2] for it in items], 8))
+    ok = np.zeros(m, dtype=np.uint8)
+    _host._check(_host.lib().mpcxh_edvss_verify_batch(threshold, m, n_vs, V.ctypes.data, I.ctypes.data, iw,
+                                                      S.ctypes.data, ok.ctypes.data))
+    return [bool(x) for x in ok]
+
+
+def edvss_public_shares_batch(threshold: int, ids: Sequence[int], vs) -> List[tuple]:
+    """vs[session][party][k] -> [(Vc, X)] per session, as public_shares_batch."""
+    n, m, t1 = len(ids), len(vs), threshold + 1
+    if any(len(sess) != n or any(len(v) != t1 for v in sess) for sess in vs):
+        raise ValueError("vs must be [session][party][threshold + 1]")
+    I, iw = _ids(ids)
+    V = _points_in([P for sess in vs for v in sess for P in v])
+    vc = np.zeros((max(m, 1), max(t1, 1) * 16), dtype="<u4")
+    xs = np.zeros((max(m, 1), max(n, 1) * 16), dtype="<u4")
+    _host._check(_host.lib().mpcxh_edvss_public_shares_batch(threshold, n, I.ctypes.data, iw, m, V.ctypes.data,
+                                                             vc.ctypes.data, xs.ctypes.data))
+    return [(_ed_points_out(vc[s]), _ed_points_out(xs[s])) for s in range(m)]
+
+
+def edvss_reconstruct_batch(items: Sequence[Sequence[tuple]]) -> List[Optional[int]]:
+    """(Shares).ReConstruct mod L per item, as reconstruct_batch (no device needed)."""
+    m = len(items)
+    if m == 0:
+        return []
+    k = len(items[0])
+    if any(len(it) != k for it in items):
+        raise ValueError("items must carry the same number of shares")
+    I, iw = _ids([i for it in items for i, _ in it])
+    S = np.ascontiguousarray(ints_to_words([s for it in items for _, s in it], 8))
+    out = np.zeros((m, 8), dtype="<u4")
+    ok = np.zeros(m, dtype=np.uint8)
+    _host._check(_host.lib().mpcxh_edvss_reconstruct_batch(m, k, I.ctypes.data, iw, S.ctypes.data, out.ctypes.data,
+                                                           ok.ctypes.data))
+    return [v if o else None for v, o in zip(words_to_ints(out), ok)]

@@ -590,6 +590,74 @@ class LocalPartySaveData:
                 "Beta": self.Beta, "p": self.P, "q": self.Q}
 
 
+def _ed_point_json(p: Optional[Tuple[int, int]]):
+    return None if p is None else {"Curve": "ed25519", "Coords": [p[0], p[1]]}
+
+
+@dataclass
+class EddsaLocalPartySaveData:
+    """tss-lib v2 eddsa/keygen/save_data.go ``LocalPartySaveData``, what mpcium
+    stores as JSON under ``eddsa:<wallet>``
+    (ref:pkg/mpc/eddsa_keygen_session.go) and reloads for signing and
+    resharing: LocalSecrets {Xi, ShareID} promoted to the top level, then Ks,
+    BigXj and EDDSAPub, points as {"Curve": "ed25519", "Coords": [x, y]}
+    (upstream, verify). big.Int fields are bare JSON numbers."""
+    Xi: Optional[int]
+    ShareID: Optional[int]
+    Ks: List[Optional[int]]
+    BigXj: List[Optional[Tuple[int, int]]]
+    EDDSAPub: Optional[Tuple[int, int]]
+
+    @classmethod
+    def from_json(cls, raw) -> "EddsaLocalPartySaveData":
+        try:
+            d = json.loads(raw) if isinstance(raw, (bytes, str)) else raw
+        except ValueError as e:
+            raise WireError(f"invalid JSON: {e}") from None
+        if not isinstance(d, dict):
+            raise WireError("LocalPartySaveData must be a JSON object")
+        for p in list(d.get("BigXj") or []) + [d.get("EDDSAPub")]:
+            if p is not None and p.get("Curve") != "ed25519":
+                raise WireError(f"an EdDSA key's point is on curve {p.get('Curve')!r}")
+        return cls(Xi=_opt_int(d.get("Xi")), ShareID=_opt_int(d.get("ShareID")), Ks=_ints(d.get("Ks")) or [],
+                   BigXj=[_point(p) for p in (d.get("BigXj") or [])], EDDSAPub=_point(d.get("EDDSAPub")))
+
+    def to_json(self) -> bytes:
+        d = {"Xi": self.Xi, "ShareID": self.ShareID, "Ks": self.Ks,
+             "BigXj": [_ed_point_json(p) for p in self.BigXj], "EDDSAPub": _ed_point_json(self.EDDSAPub)}
+        return json.dumps(d, separators=(",", ":")).encode()
+
+    def party_index(self) -> int:
+        """Position of this party in Ks (tss-lib: the sorted party keys)."""
+        try:
+            return self.Ks.index(self.ShareID)
+        except ValueError:
+            raise WireError("ShareID not found in Ks") from None
+
+    @classmethod
+    def from_keygen(cls, wallet: dict) -> List["EddsaLocalPartySaveData"]:
+        """One save data per party from a wallet of mpcium_amd.eddsa.keygen_batch
+        or reshare_batch ({"ids", "shares", "pk", "X"})."""
+        return [cls(Xi=x, ShareID=i, Ks=list(wallet["ids"]), BigXj=list(wallet["X"]), EDDSAPub=tuple(wallet["pk"]))
+                for i, x in zip(wallet["ids"], wallet["shares"])]
+
+    @staticmethod
+    def signing_wallet(parties: Sequence["EddsaLocalPartySaveData"], msg: bytes, session: bytes, readers) -> dict:
+        """The mpcium_amd.eddsa.sign_batch wallet of the signers `parties`
+        (threshold + 1 save data of one key, in signing order)."""
+        if not parties:
+            raise WireError("no signers")
+        pub, ks = parties[0].EDDSAPub, parties[0].Ks
+        if pub is None or any(p.EDDSAPub != pub or p.Ks != ks for p in parties):
+            raise WireError("the save data belong to different keys")
+        if any(p.Xi is None or p.ShareID is None for p in parties) or len({p.ShareID for p in parties}) != len(parties):
+            raise WireError("a signer's Xi or ShareID is missing or repeated")
+        for p in parties:
+            p.party_index()
+        return {"ids": [p.ShareID for p in parties], "shares": [p.Xi for p in parties], "pk": pub, "msg": msg,
+                "session": session, "readers": list(readers)}
+
+
 # --------------------------------------------------------------------------
 # Batch collection across wallets
 # --------------------------------------------------------------------------

@@ -22,6 +22,14 @@ the same run on the same box, k_ec_msm on secp256k1 items of the same shape.
 2 of 3 with its share spent inside the GPU batches.
 
     python tools/ec_bench.py --curve ed25519 --points 16 --sizes 2560,25600 --sign-wallets 10000
+
+--admit times k_ed_admit (mpcx_ed_admit_batch, clear = 1) and, in the same run
+on the same points, one-point k_ed_msm items with the integer scalar 8 c
+(c = 8^-1 mod L), every repetition's kernel time listed. --keygen-sessions N
+adds the wall time of one eddsa.keygen_batch over N sessions at 2 of 3 with
+its share spent inside the GPU batches.
+
+    python tools/ec_bench.py --admit --sizes 2560,25600 --keygen-sessions 10000
 """
 import argparse
 import json
@@ -43,6 +51,10 @@ def main():
     ap.add_argument("--curve", choices=("secp256k1", "ed25519"), default="secp256k1")
     ap.add_argument("--sign-wallets", type=int, default=0,
                     help="with --curve ed25519: also time eddsa.sign_batch over this many wallets at 2 of 3")
+    ap.add_argument("--admit", action="store_true",
+                    help="time k_ed_admit (clear = 1) and the one-point k_ed_msm route with the scalar 8 c")
+    ap.add_argument("--keygen-sessions", type=int, default=0,
+                    help="time eddsa.keygen_batch over this many sessions at 2 of 3")
     args = ap.parse_args()
     from mpcium_amd import mpcx
     from oracle import tss_ref as T
@@ -62,6 +74,10 @@ def main():
         k = [x for x in ks["kernels"] if x["kind"] == kind][0]
         return k["kernel_ms"] / args.reps, k["launches"] // args.reps
 
+    if args.admit or args.keygen_sessions:
+        admit_rows(args, mpcx, rng, out)
+        print(json.dumps(out))
+        return
     if args.curve == "ed25519":
         ed25519_rows(args, mpcx, T, rng, pts, timed, out)
         print(json.dumps(out))
@@ -173,6 +189,69 @@ def ed25519_rows(args, mpcx, T, rng, secp_pts, timed, out):
         row = {"sign_batch_wallets": W, "signers": 2, "wall_s": round(wall, 4), "gpu_batches_s": round(r["gpu_s"], 4),
                "gpu_share": round(r["gpu_s"] / wall, 3), "kernel_ms": round(k["kernel_ms"], 3),
                "launches": k["launches"], "signatures_per_s": round(W / wall)}
+        out["rows"].append(row)
+        print(json.dumps(row), flush=True)
+
+
+def admit_rows(args, mpcx, rng, out):
+    """--admit: per size, every repetition's kernel ms of k_ed_admit with clear = 1
+    and, in the same run on the same points, of one-point k_ed_msm items with the
+    integer scalar 8 c (c = 8^-1 mod L), the route without the admission kernel.
+    --keygen-sessions N: wall and GPU time of one 2-of-3 keygen_batch."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import time
+
+    import ed_model as M
+    c8 = 8 * pow(8, -1, M.L)
+    small = M.small_order_points()
+    base = [M.mul(rng.randrange(1, M.L), M.BASE) for _ in range(64)]
+    pool = [M.add(Q, small[i % 8]) for i, Q in enumerate(base)]
+
+    def reps(kind, fn):
+        ms = []
+        mpcx.set_option("kernel_stats", 1)
+        for _ in range(args.reps):
+            mpcx.kernel_stats(reset=True)
+            fn()
+            ms.append(round(sum(k["kernel_ms"] for k in mpcx.kernel_stats()["kernels"] if k["kind"] == kind), 4))
+        mpcx.set_option("kernel_stats", 0)
+        return ms
+
+    for size in (int(x) for x in args.sizes.split(",")) if args.admit else ():
+        pts = [pool[(i * 7) % 64] for i in range(size)]
+        items = [(None, [(c8, Q)]) for Q in pts]
+        got, status = mpcx.ed_admit_batch(pts)  # warm-up + check
+        assert status == [0] * size and got == [base[(i * 7) % 64] for i in range(size)]
+        assert mpcx.ed_msm_batch(items) == got
+        for name, kind, fn in (("k_ed_admit", "ed_admit", lambda: mpcx.ed_admit_batch(pts)),
+                               ("k_ed_msm, 1 point, scalar 8c", "ed_msm", lambda: mpcx.ed_msm_batch(items))):
+            ms = reps(kind, fn)
+            row = {"items": size, "kernel": name, "kernel_ms": ms, "median_ms": sorted(ms)[len(ms) // 2],
+                   "min_ms": min(ms), "max_ms": max(ms)}
+            out["rows"].append(row)
+            print(json.dumps(row), flush=True)
+    if args.keygen_sessions:
+        from mpcium_amd import eddsa, host
+        host.init(0)
+        S, ids = args.keygen_sessions, [1, 2, 3]
+        ss = [{"session": rng.randbytes(32), "readers": [3 * s + 1, 3 * s + 2, 3 * s + 3]} for s in range(S)]
+        eddsa.keygen_batch(ss[:256], 1, ids)  # warm-up
+        mpcx.set_option("kernel_stats", 1)
+        mpcx.kernel_stats(reset=True)
+        t0 = time.perf_counter()
+        r = eddsa.keygen_batch(ss, 1, ids)
+        wall = time.perf_counter() - t0
+        ks = mpcx.kernel_stats()
+        mpcx.set_option("kernel_stats", 0)
+        assert r["status"] == [0] * S
+        for s in range(0, S, max(1, S // 6)):
+            w = r["wallets"][s]
+            assert M.mul(w["shares"][1], M.BASE) == w["X"][1]
+        kern = {k["kind"]: (round(k["kernel_ms"], 3), k["launches"]) for k in ks["kernels"]
+                if k["kind"] in ("ed_msm", "ed_admit")}
+        row = {"keygen_sessions": S, "threshold": 1, "parties": 3, "wall_s": round(wall, 4),
+               "gpu_batches_s": round(r["gpu_s"], 4), "gpu_share": round(r["gpu_s"] / wall, 3),
+               "kernel_ms_launches": kern, "keygens_per_s": round(S / wall)}
         out["rows"].append(row)
         print(json.dumps(row), flush=True)
 

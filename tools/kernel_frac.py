@@ -25,6 +25,8 @@ def kname(kind, geom):
         return "k_ec_msm"
     if kind == "ed_msm":
         return "k_ed_msm"
+    if kind == "ed_admit":
+        return "k_ed_admit"
     P, K, G = GEOM[geom]
     return f"k_{kind}<{P}, {K}, {G},"
 
