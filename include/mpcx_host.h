@@ -38,6 +38,12 @@
  *                                /root/reference/pkg/mpc/eddsa_keygen_session.go
  *   mpcxh_eddsa_reshare_batch    up:eddsa/resharing, called through
  *                                /root/reference/pkg/mpc/eddsa_resharing_session.go
+ *   mpcxh_paillier_prove_batch,  up:crypto/paillier/paillier.go (*PrivateKey).Proof,
+ *   mpcxh_paillier_proof_verify_batch  (*Proof).Verify (keygen rounds 3 and 4)
+ *   mpcxh_ecdsa_keygen_batch     up:ecdsa/keygen round_1.go .. round_4.go, called through
+ *                                /root/reference/pkg/mpc/ecdsa_keygen_session.go
+ *   mpcxh_ecdsa_sign_batch       up:ecdsa/signing prepare.go .. finalize.go on stored keys,
+ *                                /root/reference/pkg/mpc/ecdsa_signing_session.go
  */
 #ifndef MPCX_HOST_H_
 #define MPCX_HOST_H_
@@ -244,6 +250,21 @@ int mpcxh_fac_prove_batch(uint32_t w, const uint8_t* sessions, uint32_t session_
 int mpcxh_fac_verify_batch(uint32_t w, const uint8_t* sessions, uint32_t session_len, const uint32_t* N0,
                            const uint32_t* NCap, const uint32_t* s, const uint32_t* t, uint32_t count,
                            const uint32_t* pf, const uint8_t* v_neg, uint8_t* ok);
+/* The Paillier key proof of keygen rounds 3 and 4 (up:crypto/paillier/paillier.go
+ * (*PrivateKey).Proof / (*Proof).Verify, 13 iterations; restated as recalled:
+ * upstream, verify -- csrc/host/proofs.hpp has GenerateXs): `count` proofs under
+ * one key N = P Q, proof i bound to k[i] (w words: the prover's party id) and
+ * the ECDSA public key pub[i] (16 words x|y). y receives / holds count x 13 x w
+ * words. The 13 x count exponentiations are one GPU launch step (the prover's
+ * by CRT over P and Q). ok[i] = 0 when a prime below 1000 divides N or some
+ * y_k^N mod N differs from GenerateXs' x_k. retries (or NULL) receives each
+ * proof's final GenerateXs retry counter. */
+#define MPCXH_PAILLIER_PROOF_ITERATIONS 13
+int mpcxh_paillier_prove_batch(uint32_t w, const uint32_t* N, const uint32_t* P, const uint32_t* Q, uint32_t count,
+                               const uint32_t* k /* count x w */, const uint32_t* pub /* count x 16 */,
+                               uint32_t* y /* count x 13 x w */, uint32_t* retries /* count */);
+int mpcxh_paillier_proof_verify_batch(uint32_t w, const uint32_t* N, uint32_t count, const uint32_t* k,
+                                      const uint32_t* pub, const uint32_t* y, uint8_t* ok);
 
 /* ---------------------------------------------------------------- Feldman VSS
  * Batched mirror of tss-lib v2.0.2's up:crypto/vss/feldman_vss.go at any
@@ -495,6 +516,75 @@ int mpcxh_bench_keygen_proofs(uint32_t w, const mpcxh_party_t* parties, uint32_t
 int mpcxh_bench_keygen_reshare(uint32_t w, const mpcxh_party_t* parties, uint32_t n_parties, uint32_t sessions,
                                uint64_t seed, uint32_t wave_sessions, int reshare_mix, int64_t tamper_session,
                                double* stats_out, uint32_t* trace_out);
+
+/* ---------------------------------------------------------------- ECDSA keygen
+ * words per party of a traced keygen session: u_i (8), the commitment C_i (8),
+ * V_i0..V_it (16 each), the shares s_i0..s_i,n-1 as sent (8 each), then 8-word
+ * SHA512_256i digests: its DLN proof (h1, h2, alpha), its DLN proof (h2, h1,
+ * beta), its Mod proof, its Fac proof to party 0..n-1 (zero at its own index) --
+ * the digests of mpcxh_bench_keygen_proofs' trace -- and its Paillier proof
+ * (y_0..y_12; zero when the session did not reach it) */
+#define MPCXH_ECDSA_KEYGEN_TRACE_WORDS(t, n) (16u + 16u * ((t) + 1u) + 8u * (n) + 8u * (4u + (n)))
+/* up:ecdsa/keygen rounds 1-4 (csrc/host/ecdsa_keygen.hpp; restated as recalled:
+ * upstream, verify) for `count` sessions over one committee of n_parties
+ * (2..16) nodes at threshold t (1 <= t < n_parties), every party replayed in
+ * process: parties[i] is node i's LocalPreParams (w >= 64 words per integer),
+ * ids its party id (id_words 1..16 words, used mod q; zero or equal ids are
+ * MPCX_EINVAL). Round 2's checks of the committee (N_j and N~_j of 2048 bits,
+ * h1_j != h2_j, no N~, h1 or h2 used twice) are made once and fail the call
+ * with MPCX_EINVAL. Per session: session bytes (session_len each; party i
+ * proves under session || big.Int(i).Bytes()) and one reader per party.
+ * status[s] = 0 with pub[s] (ECDSAPub), x[s][j] (party j's Xi) and X[s][j]
+ * (BigXj), or the round that aborted it -- 2 (a DLN proof), 3 (the
+ * decommitment, its points, the Mod proof, a Fac proof or a share), 4 (the
+ * Paillier proof) -- with culprit[s] the lowest party whose message failed and
+ * the outputs zero; culprit is 255 otherwise. The other sessions are
+ * unaffected. Every proof kind of a party is one batch over the sessions, and
+ * every point equation of a step one GPU batch over the sessions, dealers and
+ * receivers. trace_flags / trace as mpcxh_eddsa_keygen_batch, n_parties x
+ * MPCXH_ECDSA_KEYGEN_TRACE_WORDS(t, n_parties) words per flagged session. Test
+ * hooks on dealer 0 of session tamper_session (-1 / 0 for none): 1 shifts a
+ * response of its first DLN proof (round 2), 2 swaps two coordinates of its
+ * decommitment (round 3), 3 shifts the share s_01 (round 3), 4 shifts y_0 of
+ * its Paillier proof (round 4). flags: 0, or
+ * MPCXH_ECDSA_KEYGEN_SERIAL_LAUNCHES to issue every launch of the call after
+ * the one before instead of running the parties' batches side by side: the
+ * number of kernel launches then depends on the inputs alone (concurrent
+ * launches are merged by the coalescer as they happen to meet), at the price
+ * of the overlap. gpu_s (or NULL) receives the wall time inside the GPU batch
+ * calls. */
+#define MPCXH_ECDSA_KEYGEN_SERIAL_LAUNCHES 1u
+int mpcxh_ecdsa_keygen_batch(uint32_t w, const mpcxh_party_t* parties, uint32_t n_parties, uint32_t threshold,
+                             const uint32_t* ids /* n_parties x id_words */, uint32_t id_words, uint32_t count,
+                             const uint8_t* sessions /* count x session_len */, uint32_t session_len,
+                             const mpcxh_reader_t* readers /* count x n_parties */, const uint8_t* trace_flags,
+                             int64_t tamper_session, int tamper_kind, uint32_t flags, uint8_t* status /* count */,
+                             uint8_t* culprit /* count */, uint32_t* pub /* count x 16 */,
+                             uint32_t* x /* count x n_parties x 8 */, uint32_t* X /* count x n_parties x 16 */,
+                             uint32_t* trace, double* gpu_s);
+/* GG18 signing on stored wallets: mpcxh_bench_signing's rounds (the same code)
+ * on the caller's key shares, messages and session ids. Every wallet is signed
+ * by the same `signers` (2..n_nodes) nodes, sks[i] / dlns[i] the keys of signer
+ * i. Per wallet: the signers' party ids (id_words 1..16 words each, used mod q),
+ * their Shamir shares x_i and BigX_i = x_i G, ECDSAPub, the message as an
+ * integer < q (8 words) and 32 session bytes. w_i = lambda_i x_i with lambda_i
+ * the Lagrange weight at 0 over the wallet's signer ids, W_i = lambda_i BigX_i
+ * (one GPU point batch over all wallets and signers), X = ECDSAPub. The
+ * ephemeral randomness is the driver's: CounterDRBG(mix(seed, wallet, 0xFFFF,
+ * 0)) draws k_i then gamma_i per signer; the pair and GG18 readers are
+ * mpcxh_bench_signing's. status[wi] = 0 with r, s (8 words each, low-s) and
+ * recid, or no signature (zeros): 1 an MtA proof or decryption was refused, 2
+ * a round 5-9 check failed, 3 the signature failed ecdsa.Verify under
+ * ECDSAPub; the other wallets are unaffected. Malformed input (ids zero or
+ * equal mod q, msg >= q, a point off the curve) is MPCX_EINVAL. stats_out (or
+ * NULL) and trace_wallets / trace_out as mpcxh_bench_signing. */
+int mpcxh_ecdsa_sign_batch(uint32_t w, const mpcxh_paillier_t* sks, const mpcxh_dln_t* dlns, uint32_t n_nodes,
+                           uint32_t signers, uint32_t wallets, const uint32_t* ids /* wallets x signers x id_words */,
+                           uint32_t id_words, const uint32_t* x /* wallets x signers x 8 */,
+                           const uint32_t* BigX /* wallets x signers x 16 */, const uint32_t* pub /* wallets x 16 */,
+                           const uint32_t* msgs /* wallets x 8 */, const uint8_t* sessions /* wallets x 32 */,
+                           uint64_t seed, uint8_t* status, uint32_t* r, uint32_t* s, uint32_t* recid,
+                           double* stats_out, uint32_t trace_wallets, uint32_t* trace_out);
 
 /* Host-side helpers of the MtA path, exported as test hooks (no GPU needed):
  * common.SHA512_256i / SHA512_256i_TAGGED (tag == NULL: untagged) over count

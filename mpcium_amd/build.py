@@ -26,7 +26,7 @@ SOURCE_HDRS = {"mpcx_ec.hip": ["mpcx_ec_fe.hpp"], "mpcx_ec_msm.hip": ["mpcx_ec_f
                "mpcx_ec_probe.hip": ["mpcx_ec_fe.hpp"], "mpcx_ed_msm.hip": ["mpcx_ed_fe.hpp"],
                "mpcx_ed_probe.hip": ["mpcx_ed_fe.hpp"], "mpcx_ed_admit.hip": ["mpcx_ed_fe.hpp"]}
 HOST_SRCS = ["host/bignum.cpp", "host/engine.cpp", "host/modint.cpp", "host/paillier.cpp", "host/safeprime.cpp",
-             "host/tsscommon.cpp", "host/secp256k1.cpp", "host/mta.cpp", "host/proofs.cpp", "host/vss.cpp", "host/ed25519.cpp", "host/eddsa.cpp", "host/edvss.cpp", "host/eddsa_keygen.cpp", "host/signing.cpp", "host/keygenload.cpp",
+             "host/tsscommon.cpp", "host/secp256k1.cpp", "host/mta.cpp", "host/proofs.cpp", "host/vss.cpp", "host/ed25519.cpp", "host/eddsa.cpp", "host/edvss.cpp", "host/eddsa_keygen.cpp", "host/ecdsa_keygen.cpp", "host/signing.cpp", "host/keygenload.cpp",
              "host/hostprof.cpp", "host/gorand.cpp", "host/capi.cpp"]
 
 

@@ -26,6 +26,7 @@
 #include "eddsa.hpp"
 #include "eddsa_keygen.hpp"
 #include "edvss.hpp"
+#include "ecdsa_keygen.hpp"
 
 using namespace mpcx::host;
 
@@ -1040,6 +1041,8 @@ int mpcxh_random_draws(uint64_t seed, const uint32_t* less_than, uint32_t w, int
   });
 }
 
+static void signing_stats_out(const signing::MtaStats& st, double* stats_out);
+
 int mpcxh_bench_signing(uint32_t w, const mpcxh_paillier_t* sks, const mpcxh_dln_t* dlns, uint32_t n_nodes,
                         uint32_t signers, uint32_t wallets, uint64_t seed, double* stats_out, uint32_t trace_wallets,
                         uint32_t* trace_out, int64_t tamper_wallet, int tamper_kind) {
@@ -1055,11 +1058,61 @@ int mpcxh_bench_signing(uint32_t w, const mpcxh_paillier_t* sks, const mpcxh_dln
     std::vector<uint32_t> tr;
     const auto st =
         signing::RunSigning(nodes, (int)signers, wallets, seed, trace_wallets, &tr, tamper_wallet, tamper_kind);
-    const double v[MPCXH_SIGNING_STATS] = {st.round1_s, st.round2_s, st.round3_s, st.total_s, (double)st.wallets,
-                                           (double)st.sessions, (double)st.errors, (double)st.relation_failures,
-                                           st.engine_busy_s, st.finalize_s, (double)st.signatures,
-                                           (double)st.verified, st.alg_macs, (double)st.aborted};
-    std::memcpy(stats_out, v, sizeof v);
+    signing_stats_out(st, stats_out);
+    if (trace_wallets) std::memcpy(trace_out, tr.data(), tr.size() * sizeof(uint32_t));
+  });
+}
+
+static void signing_stats_out(const signing::MtaStats& st, double* stats_out) {
+  const double v[MPCXH_SIGNING_STATS] = {st.round1_s, st.round2_s, st.round3_s, st.total_s, (double)st.wallets,
+                                         (double)st.sessions, (double)st.errors, (double)st.relation_failures,
+                                         st.engine_busy_s, st.finalize_s, (double)st.signatures,
+                                         (double)st.verified, st.alg_macs, (double)st.aborted};
+  std::memcpy(stats_out, v, sizeof v);
+}
+
+int mpcxh_ecdsa_sign_batch(uint32_t w, const mpcxh_paillier_t* sks, const mpcxh_dln_t* dlns, uint32_t n_nodes,
+                           uint32_t signers, uint32_t wallets, const uint32_t* ids, uint32_t id_words,
+                           const uint32_t* x, const uint32_t* BigX, const uint32_t* pub, const uint32_t* msgs,
+                           const uint8_t* sessions, uint64_t seed, uint8_t* status, uint32_t* r, uint32_t* s,
+                           uint32_t* recid, double* stats_out, uint32_t trace_wallets, uint32_t* trace_out) {
+  return guard([&] {
+    check_width(w);
+    if (signers < 2 || signers > n_nodes) throw std::invalid_argument("signers must be in [2, nodes]");
+    if (id_words < 1 || id_words > 16) throw std::invalid_argument("ecdsa sign: id_words outside [1, 16]");
+    if (wallets && (!ids || !x || !BigX || !pub || !msgs || !sessions || !status || !r || !s || !recid))
+      throw std::invalid_argument("null buffer");
+    if (trace_wallets && !trace_out) throw std::invalid_argument("null trace_out");
+    std::vector<signing::NodeKeys> nodes(signers);  // the signers' keys, in the order of the wallets' ids
+    for (uint32_t i = 0; i < signers; ++i) {
+      nodes[i].sk = paillier_from(&sks[i], w);
+      nodes[i].dln = dln_from(&dlns[i], w);
+    }
+    std::vector<signing::StoredWallet> ws(wallets);
+    for (uint32_t wi = 0; wi < wallets; ++wi) {
+      signing::StoredWallet& sw = ws[wi];
+      const size_t b = (size_t)wi * signers;
+      sw.ids = nats(ids + b * id_words, id_words, signers);
+      sw.x = nats(x + b * 8, 8, signers);
+      sw.BigX = points_from(BigX + b * 16, signers);
+      sw.pub = points_from(pub + (size_t)wi * 16, 1)[0];
+      auto below_p = [](const uint32_t* c) { return Nat::from_words(c, 8) < secp::FieldP(); };  // NewECPoint
+      bool in_field = below_p(pub + (size_t)wi * 16) && below_p(pub + (size_t)wi * 16 + 8);
+      for (size_t c = 0; c < 2 * (size_t)signers; ++c) in_field = in_field && below_p(BigX + b * 16 + c * 8);
+      if (!in_field) throw std::invalid_argument("ecdsa sign: a point coordinate is not below p");
+      sw.msg = Nat::from_words(msgs + (size_t)wi * 8, 8);
+      sw.session.assign(sessions + (size_t)wi * 32, sessions + (size_t)(wi + 1) * 32);
+    }
+    signing::StoredResult out;
+    std::vector<uint32_t> tr;
+    const auto st = signing::SignStored(nodes, ws, seed, &out, trace_wallets, &tr);
+    for (uint32_t wi = 0; wi < wallets; ++wi) {
+      status[wi] = out.status[wi];
+      out.r[wi].to_words(r + (size_t)wi * 8, 8);
+      out.s[wi].to_words(s + (size_t)wi * 8, 8);
+      recid[wi] = out.recid[wi];
+    }
+    if (stats_out) signing_stats_out(st, stats_out);
     if (trace_wallets) std::memcpy(trace_out, tr.data(), tr.size() * sizeof(uint32_t));
   });
 }
@@ -1182,12 +1235,50 @@ int mpcxh_fac_verify_batch(uint32_t w, const uint8_t* sessions, uint32_t session
   });
 }
 
+static std::vector<proofs::PaillierStatement> paillier_statements(uint32_t w, uint32_t count, const uint32_t* k,
+                                                                  const uint32_t* pub) {
+  if (count && (!k || !pub)) throw std::invalid_argument("null buffer");
+  std::vector<proofs::PaillierStatement> st(count);
+  for (uint32_t i = 0; i < count; ++i) {
+    st[i].k = Nat::from_words(k + (size_t)i * w, w);
+    st[i].X = Nat::from_words(pub + (size_t)i * 16, 8);
+    st[i].Y = Nat::from_words(pub + (size_t)i * 16 + 8, 8);
+  }
+  return st;
+}
+
+int mpcxh_paillier_prove_batch(uint32_t w, const uint32_t* N, const uint32_t* P, const uint32_t* Q, uint32_t count,
+                               const uint32_t* k, const uint32_t* pub, uint32_t* y, uint32_t* retries) {
+  return guard([&] {
+    check_pw(w);
+    if (count && !y) throw std::invalid_argument("null buffer");
+    const auto st = paillier_statements(w, count, k, pub);
+    const Nat n = one_nat(N, w);
+    std::vector<uint32_t> rt;
+    const auto pf = proofs::PaillierProveBatch(n, one_nat(P, w), one_nat(Q, w), st, retries ? &rt : nullptr);
+    for (uint32_t i = 0; i < count; ++i) store(pf[i].Y, y + (size_t)i * proofs::kPaillierIterations * w, w);
+    if (retries) std::copy(rt.begin(), rt.end(), retries);
+  });
+}
+
+int mpcxh_paillier_proof_verify_batch(uint32_t w, const uint32_t* N, uint32_t count, const uint32_t* k,
+                                      const uint32_t* pub, const uint32_t* y, uint8_t* ok) {
+  return guard([&] {
+    check_pw(w);
+    if (count && (!y || !ok)) throw std::invalid_argument("null buffer");
+    const auto st = paillier_statements(w, count, k, pub);
+    std::vector<proofs::PaillierProof> pf(count);
+    for (uint32_t i = 0; i < count; ++i)
+      pf[i].Y = nats(y + (size_t)i * proofs::kPaillierIterations * w, w, proofs::kPaillierIterations);
+    const auto v = proofs::PaillierVerifyBatch(one_nat(N, w), st, pf);
+    std::memcpy(ok, v.data(), count);
+  });
+}
+
 }  // extern "C"
 
 namespace {
-keygenload::ProofStats bench_config5(uint32_t w, const mpcxh_party_t* parties, uint32_t n_parties, uint32_t sessions,
-                                     uint64_t seed, uint32_t wave_sessions, int mix, uint32_t* trace_out,
-                                     int64_t tamper = -1) {
+std::vector<keygenload::PartyKeys> parties_from(uint32_t w, const mpcxh_party_t* parties, uint32_t n_parties) {
   if (w < 64) throw std::invalid_argument("party integer width must be >= 64 words");
   if (!parties) throw std::invalid_argument("null argument");
   std::vector<keygenload::PartyKeys> ps(n_parties);
@@ -1204,6 +1295,12 @@ keygenload::ProofStats bench_config5(uint32_t w, const mpcxh_party_t* parties, u
     ps[i].p = Nat::from_words(a.p, w);
     ps[i].q = Nat::from_words(a.q, w);
   }
+  return ps;
+}
+keygenload::ProofStats bench_config5(uint32_t w, const mpcxh_party_t* parties, uint32_t n_parties, uint32_t sessions,
+                                     uint64_t seed, uint32_t wave_sessions, int mix, uint32_t* trace_out,
+                                     int64_t tamper = -1) {
+  const std::vector<keygenload::PartyKeys> ps = parties_from(w, parties, n_parties);
   std::vector<uint32_t> tr;
   const auto st = keygenload::RunKeygenProofs(ps, sessions, seed, wave_sessions, trace_out ? &tr : nullptr, mix, tamper);
   if (trace_out) std::memcpy(trace_out, tr.data(), tr.size() * sizeof(uint32_t));
@@ -1239,5 +1336,74 @@ int mpcxh_bench_keygen_reshare(uint32_t w, const mpcxh_party_t* parties, uint32_
     const auto st =
         bench_config5(w, parties, n_parties, sessions, seed, wave_sessions, reshare_mix, trace_out, tamper_session);
     keygen_stats(st, stats_out);
+  });
+}
+
+// ------------------------------------------------------------------ ECDSA keygen
+int mpcxh_ecdsa_keygen_batch(uint32_t w, const mpcxh_party_t* parties, uint32_t n_parties, uint32_t threshold,
+                             const uint32_t* ids, uint32_t id_words, uint32_t count, const uint8_t* sessions,
+                             uint32_t session_len, const mpcxh_reader_t* rdr, const uint8_t* trace_flags,
+                             int64_t tamper_session, int tamper_kind, uint32_t flags, uint8_t* status,
+                             uint8_t* culprit, uint32_t* pub, uint32_t* x, uint32_t* X, uint32_t* trace,
+                             double* gpu_s) {
+  return guard([&] {
+    if (n_parties < 2 || n_parties > vss::kMaxTerms) throw std::invalid_argument("ecdsa keygen: 2..16 parties");
+    if (threshold < 1 || threshold >= n_parties) throw std::invalid_argument("ecdsa keygen: 1 <= threshold < parties");
+    if (id_words < 1 || id_words > 16) throw std::invalid_argument("ecdsa keygen: id_words outside [1, 16]");
+    if (tamper_kind < 0 || tamper_kind > ecdsa::kTamperPaillier)
+      throw std::invalid_argument("ecdsa keygen: unknown tamper kind");
+    if (flags & ~(uint32_t)MPCXH_ECDSA_KEYGEN_SERIAL_LAUNCHES) throw std::invalid_argument("ecdsa keygen: unknown flag");
+    if (!ids || (count && (!rdr || !status || !culprit || !pub || !x || !X || (session_len && !sessions))))
+      throw std::invalid_argument("null buffer");
+    if (gpu_s) *gpu_s = 0;
+    const std::vector<keygenload::PartyKeys> ps = parties_from(w, parties, n_parties);
+    const std::vector<Nat> idv = nats(ids, id_words, n_parties);
+    vss::CheckIndexes(idv);
+    if (!count) return;
+    size_t traced = 0;
+    for (uint32_t s = 0; trace_flags && s < count; ++s) traced += trace_flags[s] ? 1 : 0;
+    if (traced && !trace) throw std::invalid_argument("null trace buffer");
+    std::vector<CounterDRBG> drbgs;
+    const auto rd = readers(rdr, count * n_parties, &drbgs);
+    std::vector<ecdsa::KeygenSession> ss(count);
+    for (uint32_t s = 0; s < count; ++s) {
+      if (session_len) ss[s].session.assign(sessions + (size_t)s * session_len, sessions + (size_t)(s + 1) * session_len);
+      ss[s].readers.assign(rd.begin() + (long)((size_t)s * n_parties), rd.begin() + (long)((size_t)(s + 1) * n_parties));
+      ss[s].trace = trace_flags && trace_flags[s];
+    }
+    const ecdsa::KeygenResult r = ecdsa::KeygenBatch(
+        ps, ss, threshold, idv, tamper_session, tamper_kind, (flags & MPCXH_ECDSA_KEYGEN_SERIAL_LAUNCHES) != 0);
+    const uint32_t n = n_parties;
+    std::fill(pub, pub + (size_t)count * 16, 0u);
+    std::fill(x, x + (size_t)count * n * 8, 0u);
+    std::fill(X, X + (size_t)count * n * 16, 0u);
+    for (uint32_t s = 0; s < count; ++s) {
+      status[s] = r.status[s];
+      culprit[s] = r.culprit[s];
+      if (r.status[s]) continue;
+      point_out(r.pub[s], pub + (size_t)s * 16);
+      for (uint32_t j = 0; j < n; ++j) {
+        r.x[s][j].to_words(x + ((size_t)s * n + j) * 8, 8);
+        point_out(r.X[s][j], X + ((size_t)s * n + j) * 16);
+      }
+    }
+    const size_t pw = MPCXH_ECDSA_KEYGEN_TRACE_WORDS(threshold, n);
+    for (size_t q = 0; q < r.trace.size(); ++q)
+      for (uint32_t i = 0; i < n; ++i) {
+        const ecdsa::KeygenParty& p = r.trace[q][i];
+        uint32_t* o = trace + (q * n + i) * pw;
+        p.u.to_words(o, 8);
+        p.C.to_words(o + 8, 8);
+        o += 16;
+        for (uint32_t k = 0; k <= threshold; ++k, o += 16) point_out(p.V[k], o);
+        for (uint32_t j = 0; j < n; ++j, o += 8) p.shares[j].to_words(o, 8);
+        p.dln1.to_words(o, 8);
+        p.dln2.to_words(o + 8, 8);
+        p.mod.to_words(o + 16, 8);
+        o += 24;
+        for (uint32_t j = 0; j < n; ++j, o += 8) p.fac[j].to_words(o, 8);
+        p.paillier.to_words(o, 8);
+      }
+    if (gpu_s) *gpu_s = r.gpu_s;
   });
 }

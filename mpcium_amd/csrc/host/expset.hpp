@@ -22,13 +22,33 @@ namespace mpcx::host {
 // rethrows the first failure once all have finished. libmpcx runs calls from
 // different threads on different execution lanes (streams), so independent
 // launches of one protocol step overlap on the GPU instead of queueing.
+// While the calling thread holds a SerialLaunches, its ExpSets issue their
+// launches one after another: the number of kernel launches of a protocol run
+// is then a function of its inputs alone. Concurrent launches meet in the
+// coalescer (engine.cpp), which merges whatever waits when a dispatch slot
+// frees, so their number depends on timing. ecdsa::KeygenBatch holds one when
+// asked to (serial_launches: launch-count checks; DESIGN.md section 6 has its
+// cost). The depth is per thread: it covers the ExpSets run on the holder's own
+// thread, which is where every proofs::*Batch runs its set; a *Batch that ever
+// moves its ExpSet::run to a worker thread would escape it silently.
+inline int& serial_launch_depth() {
+  static thread_local int depth = 0;
+  return depth;
+}
+struct SerialLaunches {
+  SerialLaunches() { ++serial_launch_depth(); }
+  ~SerialLaunches() { --serial_launch_depth(); }
+  SerialLaunches(const SerialLaunches&) = delete;
+  SerialLaunches& operator=(const SerialLaunches&) = delete;
+};
+
 inline void run_concurrently(const std::vector<std::function<void()>>& fs) {
   if (fs.empty()) return;
   static const bool serial = [] {  // MPCX_EXPSET_SERIAL=1: one launch after another (A/B runs)
     const char* e = std::getenv("MPCX_EXPSET_SERIAL");
     return e && e[0] == '1';
   }();
-  if (serial) {
+  if (serial || serial_launch_depth() > 0) {
     for (const auto& f : fs) f();
     return;
   }

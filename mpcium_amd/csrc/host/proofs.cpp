@@ -2,7 +2,10 @@
 // mirrors (restated in oracle/proofs_ref.py).
 #include "proofs.hpp"
 
+#include <algorithm>
+#include <functional>
 #include <stdexcept>
+#include <string>
 
 #include "expset.hpp"
 #include "safeprime.hpp"
@@ -395,6 +398,148 @@ std::vector<uint8_t> FacVerifyBatch(const std::vector<Bytes>& session, const Nat
   });
   for (size_t i = 0; i < n; ++i)
     ok[i] = ok[i] && st[i].L1 == st[i].R1 && st[i].L2 == st[i].R2 && st[i].L3 == st[i].R3;
+  return ok;
+}
+
+// ================================================================ Paillier key proof
+namespace {
+
+std::vector<uint8_t> itoa_bytes(uint64_t v) {
+  const std::string s = std::to_string(v);
+  return std::vector<uint8_t>(s.begin(), s.end());
+}
+
+// GenerateXs of one statement. coprime == nullptr: the gcd test is left to the
+// caller (every x in range is taken); else it decides each candidate.
+std::vector<Nat> generate_xs(const Nat& N, const std::vector<uint8_t>& Nb, const PaillierStatement& st,
+                             const std::function<bool(const Nat&)>* coprime, uint32_t* retries) {
+  const size_t blocks = (N.bit_len() + 255) / 256;
+  const std::vector<uint8_t> kb = st.k.to_bytes_be(), xb = st.X.to_bytes_be(), yb = st.Y.to_bytes_be();
+  std::vector<Nat> xs(kPaillierIterations);
+  uint32_t n = 0;
+  std::vector<uint8_t> buf(blocks * 32);
+  for (int i = 0; i < kPaillierIterations;) {
+    const std::vector<uint8_t> ib = itoa_bytes((uint64_t)i), nb = itoa_bytes(n);
+    for (size_t j = 0; j < blocks; ++j) {
+      const std::vector<uint8_t> h = SHA512_256({ib, itoa_bytes(j), nb, kb, xb, yb, Nb});
+      std::copy(h.begin(), h.end(), buf.begin() + (long)(j * 32));
+    }
+    Nat x = Nat::from_bytes_be(buf.data(), buf.size());
+    if (!x.is_zero() && x < N && (!coprime || (*coprime)(x))) {
+      xs[(size_t)i++] = std::move(x);
+    } else {
+      ++n;
+    }
+  }
+  if (retries) *retries = n;
+  return xs;
+}
+
+}  // namespace
+
+bool GenerateXsFeasible(const Nat& N) {
+  return !N.is_zero() && (N.bit_len() + 255) / 256 * 256 - N.bit_len() <= 16;
+}
+
+std::vector<std::vector<Nat>> GenerateXsBatch(const Nat& N, const std::vector<PaillierStatement>& st,
+                                              std::vector<uint32_t>* retries) {
+  if (!GenerateXsFeasible(N)) throw std::invalid_argument("GenerateXs: N is too far below a multiple of 256 bits");
+  const size_t n = st.size();
+  const std::vector<uint8_t> Nb = N.to_bytes_be();
+  std::vector<std::vector<Nat>> xs(n);
+  std::vector<uint32_t> rt(n, 0);
+  parallel_for(n, [&](size_t i) { xs[i] = generate_xs(N, Nb, st[i], nullptr, &rt[i]); });
+  // the gcd decisions of the whole call at once; a statement with a candidate
+  // sharing a factor with N (never for an honest key) is redone one by one
+  std::vector<const Nat*> all;
+  all.reserve(n * kPaillierIterations);
+  for (const auto& v : xs)
+    for (const Nat& x : v) all.push_back(&x);
+  const std::vector<uint8_t> ok = CoprimeMany(all, N);
+  const std::function<bool(const Nat&)> cop = [&](const Nat& x) { return gcd(x, N) == Nat(1); };
+  for (size_t i = 0; i < n; ++i) {
+    bool good = true;
+    for (int k = 0; k < kPaillierIterations; ++k) good = good && ok[i * kPaillierIterations + (size_t)k];
+    if (!good) xs[i] = generate_xs(N, Nb, st[i], &cop, &rt[i]);
+  }
+  if (retries) *retries = rt;
+  return xs;
+}
+
+std::vector<PaillierProof> PaillierProveBatch(const Nat& N, const Nat& P, const Nat& Q,
+                                              const std::vector<PaillierStatement>& st,
+                                              std::vector<uint32_t>* retries, std::vector<std::vector<Nat>>* xs_out) {
+  const size_t n = st.size();
+  const Nat one(1);
+  if (P <= one || Q <= one || P * Q != N) throw std::invalid_argument("Paillier proof: N != P Q");
+  const Nat Pm1 = P - one, Qm1 = Q - one, phi = Pm1 * Qm1;
+  Nat M, qinv;
+  if (!mod_inverse(Int(N), phi, &M)) throw std::invalid_argument("Paillier proof: N not invertible mod phi");
+  if (!mod_inverse(Int(Q % P), P, &qinv)) throw std::invalid_argument("Paillier proof: P, Q not coprime");
+  const std::vector<std::vector<Nat>> xs = GenerateXsBatch(N, st, retries);
+  // y = x^M mod N by CRT (x coprime to N, so x^M mod p = x^(M mod (p - 1)) mod p)
+  const Nat mP = M % Pm1, mQ = M % Qm1;
+  std::vector<std::vector<Nat>> rP(n, std::vector<Nat>(kPaillierIterations)),
+      rQ(n, std::vector<Nat>(kPaillierIterations));
+  {
+    ExpSet sP(P), sQ(Q);
+    for (size_t i = 0; i < n; ++i)
+      for (int k = 0; k < kPaillierIterations; ++k) {
+        sP.add(xs[i][(size_t)k], mP, &rP[i][(size_t)k]);
+        sQ.add(xs[i][(size_t)k], mQ, &rQ[i][(size_t)k]);
+      }
+    run_all({&sP, &sQ});
+  }
+  std::vector<PaillierProof> out(n);
+  parallel_for(n, [&](size_t i) {
+    out[i].Y.resize(kPaillierIterations);
+    for (size_t k = 0; k < (size_t)kPaillierIterations; ++k) {
+      const Nat bp = rQ[i][k] % P;
+      const Nat d = rP[i][k] < bp ? rP[i][k] + P - bp : rP[i][k] - bp;
+      out[i].Y[k] = rQ[i][k] + Q * mulmod(d, qinv, P);
+    }
+  });
+  if (xs_out) *xs_out = xs;
+  return out;
+}
+
+std::vector<uint8_t> PaillierVerifyBatch(const Nat& N, const std::vector<PaillierStatement>& st,
+                                         const std::vector<PaillierProof>& pf,
+                                         const std::vector<std::vector<Nat>>* xs_in) {
+  const size_t n = pf.size();
+  if (st.size() != n) throw std::invalid_argument("Paillier proof verify: sizes");
+  std::vector<uint8_t> ok(n, 0);
+  if (N <= Nat(1)) return ok;
+  static const std::vector<uint32_t> small = [] {  // the primes below 1000
+    std::vector<uint32_t> p;
+    for (uint32_t v = 2; v < 1000; ++v) {
+      bool prime = true;
+      for (uint32_t d = 2; d * d <= v && prime; ++d) prime = v % d != 0;
+      if (prime) p.push_back(v);
+    }
+    return p;
+  }();
+  for (uint32_t p : small)
+    if (N.mod_u32(p) == 0) return ok;
+  if (!GenerateXsFeasible(N)) return ok;  // upstream would not return (proofs.hpp)
+  if (xs_in && xs_in->size() != n) throw std::invalid_argument("Paillier proof verify: sizes");
+  const std::vector<std::vector<Nat>> own = xs_in ? std::vector<std::vector<Nat>>() : GenerateXsBatch(N, st);
+  const std::vector<std::vector<Nat>>& xs = xs_in ? *xs_in : own;
+  std::vector<std::vector<Nat>> y(n), yN(n);
+  for (size_t i = 0; i < n; ++i) {
+    if ((int)pf[i].Y.size() != kPaillierIterations) continue;
+    ok[i] = 1;
+    y[i].resize(kPaillierIterations);
+    yN[i].resize(kPaillierIterations);
+    for (size_t k = 0; k < (size_t)kPaillierIterations; ++k) y[i][k] = pf[i].Y[k] % N;
+  }
+  ExpSet e(N);
+  for (size_t i = 0; i < n; ++i)
+    if (ok[i])
+      for (size_t k = 0; k < (size_t)kPaillierIterations; ++k) e.add(y[i][k], N, &yN[i][k]);  // y_i^N
+  e.run();
+  for (size_t i = 0; i < n; ++i)
+    for (size_t k = 0; k < (size_t)kPaillierIterations && ok[i]; ++k) ok[i] = yN[i][k] == xs[i][k];
   return ok;
 }
 

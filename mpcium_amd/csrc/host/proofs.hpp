@@ -74,4 +74,47 @@ std::vector<FacProof> FacProveBatch(const std::vector<Bytes>& session, const Nat
 std::vector<uint8_t> FacVerifyBatch(const std::vector<Bytes>& session, const Nat& N0, const Nat& NCap, const Nat& s,
                                     const Nat& t, const std::vector<FacProof>& pf);
 
+// ---- Paillier key proof (up:crypto/paillier/paillier.go (*PrivateKey).Proof /
+// (*Proof).Verify, keygen rounds 3 and 4; "upstream, verify": restated as
+// recalled, tss-lib is not vendored -- DESIGN.md section 8):
+//   GenerateXs(13, k, N, pub): for i < 13, with a retry counter n from 0 that is
+//     never reset: x = SetBytes(||_{j < blocks} SHA512_256(itoa(i), itoa(j),
+//     itoa(n), k.Bytes(), pub.X.Bytes(), pub.Y.Bytes(), N.Bytes())), blocks =
+//     ceil(N.BitLen() / 256), itoa decimal ASCII; accepted iff 0 < x < N and
+//     gcd(x, N) = 1, else n += 1 and the same i again (x >= N is common);
+//   Proof:  y_i = x_i^M mod N, M = N^-1 mod phi(N) -- by CRT over P and Q, the
+//     same integers (see ModProveBatch);
+//   Verify: no prime below 1000 divides N, and y_i^N mod N == x_i for all 13.
+// All proofs of a call are over one key: the 13 x count exponentiations are one
+// ExpSet launch step, the coprimality tests one CoprimeMany.
+constexpr int kPaillierIterations = 13;
+
+struct PaillierProof {
+  std::vector<Nat> Y;  // kPaillierIterations
+};
+struct PaillierStatement {  // k and the ECDSA public key the proof is bound to
+  Nat k, X, Y;
+};
+
+// A candidate x has 256 ceil(N.BitLen() / 256) bits, so x < N takes about 2^u
+// tries when N is u bits short of a multiple of 256: upstream's loop does not
+// end in practice for, say, a 2000-bit N. Here such an N (u > 16) is refused:
+// GenerateXsBatch and PaillierProveBatch throw std::invalid_argument,
+// PaillierVerifyBatch rejects. Keygen's committee check admits 2048-bit N only.
+bool GenerateXsFeasible(const Nat& N);
+// GenerateXs per statement; retries[i] (optional) = the final retry counter n
+std::vector<std::vector<Nat>> GenerateXsBatch(const Nat& N, const std::vector<PaillierStatement>& st,
+                                              std::vector<uint32_t>* retries = nullptr);
+// (*PrivateKey).Proof(k, pub) for every statement under the key N = P Q;
+// retries / xs (optional) receive GenerateXs' retry counters and values
+std::vector<PaillierProof> PaillierProveBatch(const Nat& N, const Nat& P, const Nat& Q,
+                                              const std::vector<PaillierStatement>& st,
+                                              std::vector<uint32_t>* retries = nullptr,
+                                              std::vector<std::vector<Nat>>* xs = nullptr);
+// (*Proof).Verify(N, k, pub); xs (optional): GenerateXsBatch(N, st) where the
+// caller has it already (a process that plays prover and verifier)
+std::vector<uint8_t> PaillierVerifyBatch(const Nat& N, const std::vector<PaillierStatement>& st,
+                                         const std::vector<PaillierProof>& pf,
+                                         const std::vector<std::vector<Nat>>* xs = nullptr);
+
 }  // namespace mpcx::host::proofs

@@ -123,10 +123,29 @@ struct Signer {
   bool ok = true;
 };
 
-}  // namespace
+// lambda_i = prod_{j != i} id_j / (id_j - id_i) mod q over a wallet's signers (ids reduced mod q)
+std::vector<Nat> lagrange_at_zero(const std::vector<Nat>& idq) {
+  const Nat& q = mta::Q();
+  std::vector<Nat> lam(idq.size());
+  for (size_t i = 0; i < idq.size(); ++i) {
+    Nat num(1), den(1);
+    for (size_t j = 0; j < idq.size(); ++j) {
+      if (j == i) continue;
+      num = (num * idq[j]) % q;
+      den = (den * ((idq[j] + q - idq[i]) % q)) % q;
+    }
+    Nat inv;
+    if (!mod_inverse(Int(den), q, &inv)) throw std::invalid_argument("signing: two signer ids are equal mod q");
+    lam[i] = (num * inv) % q;
+  }
+  return lam;
+}
 
-MtaStats RunSigning(const std::vector<NodeKeys>& nodes, int signers, size_t wallets, uint64_t seed,
-                    size_t trace_wallets, std::vector<uint32_t>* trace, int64_t tamper_wallet, int tamper_kind) {
+// RunSigning (stored == nullptr: every wallet's shares, message and session id
+// from the seed) and SignStored (the caller's) share everything from round 1 on.
+MtaStats run_signing(const std::vector<NodeKeys>& nodes, int signers, size_t wallets, uint64_t seed,
+                     const std::vector<StoredWallet>* stored, StoredResult* stored_out, size_t trace_wallets,
+                     std::vector<uint32_t>* trace, int64_t tamper_wallet, int tamper_kind) {
   if (signers < 2 || (size_t)signers > nodes.size()) throw std::invalid_argument("signers must be in [2, nodes]");
   MPCX_TRACE("run", wallets);  // timeline window of this run
   const Nat& q = mta::Q();
@@ -135,6 +154,7 @@ MtaStats RunSigning(const std::vector<NodeKeys>& nodes, int signers, size_t wall
   st.wallets = Wn;
   // per wallet and signer: k_i, gamma_i, w_i < q; W_i = w_i G; one session id per wallet
   std::vector<std::vector<Nat>> k(S, std::vector<Nat>(Wn)), g(S, std::vector<Nat>(Wn)), w(S, std::vector<Nat>(Wn));
+  std::vector<std::vector<Nat>> lam(stored ? S : 0, std::vector<Nat>(Wn));  // stored: W_i = lambda_i BigX_i
   std::vector<std::vector<secp::Affine>> Wp(S, std::vector<secp::Affine>(Wn));
   std::vector<mta::Bytes> sess(Wn);
   std::vector<Nat> msg(Wn);        // the message (tx hash as an integer < q) of each wallet's signature
@@ -142,6 +162,22 @@ MtaStats RunSigning(const std::vector<NodeKeys>& nodes, int signers, size_t wall
   parallel_for(Wn, [&](size_t wi) {
     CounterDRBG d(mix(seed, wi, 0xFFFF, 0));
     const RandFn r = d.fn();
+    if (stored) {
+      const StoredWallet& sw = (*stored)[wi];
+      std::vector<Nat> idq(S);
+      for (size_t i = 0; i < S; ++i) idq[i] = sw.ids[i] % q;
+      const std::vector<Nat> l = lagrange_at_zero(idq);
+      sess[wi] = sw.session;
+      for (size_t i = 0; i < S; ++i) {
+        k[i][wi] = GetRandomPositiveInt(r, q);
+        g[i][wi] = GetRandomPositiveInt(r, q);
+        lam[i][wi] = l[i];
+        w[i][wi] = (l[i] * (sw.x[i] % q)) % q;
+        sg[wi * S + i].rd = CounterDRBG(mix(seed, wi, 0x100 + i, 4));
+      }
+      msg[wi] = sw.msg;
+      return;
+    }
     sess[wi].resize(32);
     r(sess[wi].data(), 32);
     for (size_t i = 0; i < S; ++i) {
@@ -166,7 +202,12 @@ MtaStats RunSigning(const std::vector<NodeKeys>& nodes, int signers, size_t wall
       for (size_t wi = 0; wi < Wn; ++wi)
         for (size_t i = 0; i < S; ++i) {
           c[2 * (wi * S + i)].a = g[i][wi];
-          c[2 * (wi * S + i) + 1].a = w[i][wi];
+          if (stored) {  // W_i = lambda_i BigX_i
+            c[2 * (wi * S + i) + 1].P = (*stored)[wi].BigX[i];
+            c[2 * (wi * S + i) + 1].b = lam[i][wi];
+          } else {
+            c[2 * (wi * S + i) + 1].a = w[i][wi];
+          }
         }
       const std::vector<secp::Affine> p = secp::CombineBatch(c);
       std::vector<Nat> a4(Wn * S);
@@ -183,7 +224,7 @@ MtaStats RunSigning(const std::vector<NodeKeys>& nodes, int signers, size_t wall
           a4[wi * S + i] = GetRandomPositiveInt(r, q);              // round 4: a < q, alpha = a G
           ca[wi * S + i].a = a4[wi * S + i];
         }
-        XW[wi] = X;
+        XW[wi] = stored ? (*stored)[wi].pub : X;
       });
       const std::vector<secp::Affine> al = secp::CombineBatch(ca);
       parallel_for(Wn, [&](size_t wi) {
@@ -223,11 +264,12 @@ MtaStats RunSigning(const std::vector<NodeKeys>& nodes, int signers, size_t wall
     std::vector<mta::RangeProofAlice> pfA;
     std::vector<mta::BobMidResult> bob, bobwc;
     std::vector<Nat> alpha, mu;
+    std::vector<uint8_t> refused;  // per wallet: an MtA step of this pair returned an error
   };
   std::vector<Pair> pairs;
   for (size_t i = 0; i < S; ++i)
     for (size_t j = 0; j < S; ++j)
-      if (i != j) pairs.push_back(Pair{i, j, {}, {}, {}, {}, {}, {}});
+      if (i != j) pairs.push_back(Pair{i, j, {}, {}, {}, {}, {}, {}, {}});
   st.pairs = pairs.size();
   st.sessions = pairs.size() * Wn;
   for (auto& p : pairs) {
@@ -237,9 +279,10 @@ MtaStats RunSigning(const std::vector<NodeKeys>& nodes, int signers, size_t wall
     p.bobwc.resize(Wn);
     p.alpha.resize(Wn);
     p.mu.resize(Wn);
+    p.refused.assign(Wn, 0);
   }
   std::atomic<uint64_t> errors{0};
-  auto count_err = [&](const std::vector<uint8_t>& err) {
+  auto count_err_total = [&](const std::vector<uint8_t>& err) {
     uint64_t n = 0;
     for (auto e : err) n += e != 0;
     errors += n;
@@ -273,6 +316,7 @@ MtaStats RunSigning(const std::vector<NodeKeys>& nodes, int signers, size_t wall
       std::vector<mta::RangeProofAlice> pfA;
       std::vector<mta::BobMidResult> bob, bobwc;
       std::vector<Nat> alpha, mu;
+      std::vector<uint8_t> refused;
     };
     std::vector<Local> L(pairs.size());
     for (size_t pi = 0; pi < pairs.size(); ++pi) {
@@ -281,6 +325,7 @@ MtaStats RunSigning(const std::vector<NodeKeys>& nodes, int signers, size_t wall
       l.da.reserve(n);
       l.db.reserve(n);
       l.dbwc.reserve(n);
+      l.refused.assign(n, 0);
       for (size_t wi = lo; wi < hi; ++wi) {
         l.da.emplace_back(mix(seed, wi, p.i * 16 + p.j, 1));
         l.db.emplace_back(mix(seed, wi, p.i * 16 + p.j, 2));
@@ -301,6 +346,11 @@ MtaStats RunSigning(const std::vector<NodeKeys>& nodes, int signers, size_t wall
         const Pair& p = pairs[pi];
         Local& l = L[pi];
         prof::set_chain((int)(lo * 64 + pi));  // timeline tag: chunk start x 64 + ordered pair
+        auto count_err = [&](const std::vector<uint8_t>& err) {  // the run's total, and per wallet
+          count_err_total(err);
+          for (size_t x = 0; x < err.size() && x < n; ++x)
+            if (err[x]) l.refused[x] = 1;
+        };
         const double a0 = now();
         {  // round 1: AliceInit(k_i) to Bob j
           MPCX_TRACE("round1", n);
@@ -354,6 +404,7 @@ MtaStats RunSigning(const std::vector<NodeKeys>& nodes, int signers, size_t wall
         p.bobwc[lo + x] = std::move(l.bobwc[x]);
         p.alpha[lo + x] = std::move(l.alpha[x]);
         p.mu[lo + x] = std::move(l.mu[x]);
+        p.refused[lo + x] = l.refused[x];
       }
     }
     join_ec();
@@ -764,7 +815,59 @@ MtaStats RunSigning(const std::vector<NodeKeys>& nodes, int signers, size_t wall
   st.errors = errors.load();
   st.engine_busy_s = Engine::get().busy_seconds();
   st.alg_macs = Engine::get().alg_macs();
+  if (stored_out) {
+    stored_out->status.assign(Wn, kSignOk);
+    stored_out->r.assign(Wn, Nat());
+    stored_out->s.assign(Wn, Nat());
+    stored_out->recid.assign(Wn, 0);
+    for (size_t wi = 0; wi < Wn; ++wi) {
+      bool refused = false;
+      for (const auto& p : pairs) refused = refused || p.refused[wi];
+      uint8_t& status = stored_out->status[wi];
+      // sig_r stays zero unless the wallet passed every round 5-9 check of every
+      // signer: the finalize step above returns before fin_ok for a wallet with a
+      // failed s.ok, an infinite R or a zero r or s, and only fin_ok wallets get
+      // sig_r. A refused MtA step is reported first, whatever the later rounds
+      // made of its zeroed output.
+      if (refused) status = kSignMtaRefused;
+      else if (sig_r[wi].is_zero()) status = kSignTranscript;
+      else if (!verified[wi]) status = kSignNotVerified;
+      if (status) continue;
+      stored_out->r[wi] = sig_r[wi];
+      stored_out->s[wi] = sig_s[wi];
+      stored_out->recid[wi] = recid[wi];
+    }
+  }
   return st;
+}
+
+}  // namespace
+
+MtaStats RunSigning(const std::vector<NodeKeys>& nodes, int signers, size_t wallets, uint64_t seed,
+                    size_t trace_wallets, std::vector<uint32_t>* trace, int64_t tamper_wallet, int tamper_kind) {
+  return run_signing(nodes, signers, wallets, seed, nullptr, nullptr, trace_wallets, trace, tamper_wallet, tamper_kind);
+}
+
+MtaStats SignStored(const std::vector<NodeKeys>& nodes, const std::vector<StoredWallet>& wallets, uint64_t seed,
+                    StoredResult* out, size_t trace_wallets, std::vector<uint32_t>* trace) {
+  if (!out) throw std::invalid_argument("signing: null result");
+  const size_t S = wallets.empty() ? 2 : wallets[0].ids.size();
+  if (S < 2 || S > nodes.size()) throw std::invalid_argument("signers must be in [2, nodes]");
+  const Nat& q = mta::Q();
+  for (const StoredWallet& w : wallets) {
+    if (w.ids.size() != S || w.x.size() != S || w.BigX.size() != S)
+      throw std::invalid_argument("signing: every wallet needs the same number of ids, shares and public shares");
+    if (w.session.size() != 32) throw std::invalid_argument("signing: a session id is 32 bytes");
+    if (!(w.msg < q)) throw std::invalid_argument("signing: a message is an integer below q");
+    if (!secp::IsOnCurve(w.pub)) throw std::invalid_argument("signing: a public key is not on the curve");
+    for (size_t i = 0; i < S; ++i) {
+      if (!secp::IsOnCurve(w.BigX[i])) throw std::invalid_argument("signing: a public share is not on the curve");
+      if ((w.ids[i] % q).is_zero()) throw std::invalid_argument("signing: a signer id is 0 mod q");
+      for (size_t j = 0; j < i; ++j)
+        if (w.ids[i] % q == w.ids[j] % q) throw std::invalid_argument("signing: two signer ids are equal mod q");
+    }
+  }
+  return run_signing(nodes, (int)S, wallets.size(), seed, &wallets, out, trace_wallets, trace, -1, 0);
 }
 
 }  // namespace mpcx::host::signing

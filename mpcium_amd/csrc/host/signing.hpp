@@ -91,4 +91,37 @@ MtaStats RunSigning(const std::vector<NodeKeys>& nodes, int signers, size_t wall
                     size_t trace_wallets = 0, std::vector<uint32_t>* trace = nullptr, int64_t tamper_wallet = -1,
                     int tamper_kind = 0);
 
+// ---- the same rounds on stored wallets (keygen's LocalPartySaveData): the
+// caller's key shares, message and session id instead of seeded ones.
+// Signer i of a wallet holds the Shamir share x_i at ids[i] with BigX_i = x_i G;
+// w_i = lambda_i x_i with lambda_i = prod_{j != i} id_j / (id_j - id_i) mod q over
+// the wallet's signers, W_i = lambda_i BigX_i (all wallets' and signers' in the
+// GPU point batch that also holds Gamma_i) and X = pub (tss-lib
+// up:ecdsa/signing/prepare.go PrepareForSigning; upstream, verify). The
+// ephemeral randomness stays the driver's: the reader mix(seed, wallet, 0xFFFF,
+// 0) draws k_i then gamma_i per signer and nothing else; the pair readers and the
+// GG18 readers are RunSigning's. Everything from round 1 on, the chunk pipelines
+// and the trace layout are RunSigning's own code.
+struct StoredWallet {
+  std::vector<Nat> ids, x;           // one per signer; ids are used mod q
+  std::vector<secp::Affine> BigX;    // one per signer
+  secp::Affine pub;                  // ECDSAPub
+  Nat msg;                           // < q
+  mta::Bytes session;                // 32 bytes
+};
+// status of a stored wallet: 0 with (r, s, recid); else no signature -- an MtA
+// proof or decryption was refused (1: tss-lib aborts in round 2 or 3), a GG18
+// round 5-9 check failed (2), or the signature failed ecdsa.Verify under pub (3)
+constexpr uint8_t kSignOk = 0, kSignMtaRefused = 1, kSignTranscript = 2, kSignNotVerified = 3;
+struct StoredResult {
+  std::vector<uint8_t> status;
+  std::vector<Nat> r, s;  // zero where status != 0
+  std::vector<uint32_t> recid;
+};
+// Every wallet is signed by nodes[0..S), S = wallets[0].ids.size() in [2, nodes];
+// throws std::invalid_argument on wallets of another shape, ids that are zero or
+// equal mod q, msg >= q or a point off the curve.
+MtaStats SignStored(const std::vector<NodeKeys>& nodes, const std::vector<StoredWallet>& wallets, uint64_t seed,
+                    StoredResult* out, size_t trace_wallets = 0, std::vector<uint32_t>* trace = nullptr);
+
 }  // namespace mpcx::host::signing

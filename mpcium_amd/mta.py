@@ -49,6 +49,8 @@ SIGNATURES = [
     ("mpcxh_secp_lincomb", _i, [_vp, _vp, _vp, _u32, _vp]),
     ("mpcxh_random_draws", _i, [_u64, _vp, _u32, _i, _u32, _vp]),
     ("mpcxh_bench_signing", _i, [_u32, _vp, _vp, _u32, _u32, _u32, _u64, _vp, _u32, _vp, ctypes.c_int64, _i]),
+    ("mpcxh_ecdsa_sign_batch", _i, [_u32, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp, _vp,
+                                    _vp, _vp, _vp, _u32, _vp]),
 ]
 
 _bound = False
@@ -346,20 +348,37 @@ def bench_signing(nodes: Sequence[Dict[str, int]], signers: int, wallets: int, s
     (t < trace_wallets; spread over every concurrent wallet pipeline):
     {"wallets": [index], "pairs": [[{alpha, beta, mu, nu, digest} per traced
     wallet] per ordered pair], "sigs": [(r, s, recid)], "gg18": [digest]}."""
-    k = _Keep()
-    sks = (PaillierKey * len(nodes))(*[_paillier(k, n["N"], n["LambdaN"], n["P"], n["Q"]) for n in nodes])
-    dlns = (DLN * len(nodes))(*[_dln(k, {"NTilde": n["NTildei"], "h1": n["H1i"], "h2": n["H2i"],
-                                         "P": 2 * n["p"] + 1, "Q": 2 * n["q"] + 1}) for n in nodes])
+    k, sks, dlns = node_keys(nodes)
     st = np.zeros(len(SIGNING_STATS), dtype=np.float64)
-    npairs = signers * (signers - 1)
     tw = min(trace_wallets, wallets)
-    tr = np.zeros(max(1, npairs * tw * 40 + tw * 25), dtype="<u4")
+    tr = np.zeros(signing_trace_words(signers, tw), dtype="<u4")
     tw_idx, tk = tamper if tamper else (-1, 0)
     _check(lib().mpcxh_bench_signing(W, sks, dlns, len(nodes), signers, wallets, seed, st.ctypes.data, tw,
                                      tr.ctypes.data if tw else None, tw_idx, tk))
     stats = dict(zip(SIGNING_STATS, [float(x) for x in st]))
     if not tw:
         return stats
+    return stats, signing_trace(tr, signers, tw, wallets)
+
+
+def node_keys(nodes: Sequence[Dict[str, int]]):
+    """(keep, mpcxh_paillier_t array, mpcxh_dln_t array) of signing nodes given
+    as node_preparams.json dicts; hold `keep` for the duration of the call."""
+    k = _Keep()
+    sks = (PaillierKey * len(nodes))(*[_paillier(k, n["N"], n["LambdaN"], n["P"], n["Q"]) for n in nodes])
+    dlns = (DLN * len(nodes))(*[_dln(k, {"NTilde": n["NTildei"], "h1": n["H1i"], "h2": n["H2i"],
+                                         "P": 2 * n["p"] + 1, "Q": 2 * n["q"] + 1}) for n in nodes])
+    return k, sks, dlns
+
+
+def signing_trace_words(signers: int, tw: int) -> int:
+    return max(1, signers * (signers - 1) * tw * 40 + tw * 25)
+
+
+def signing_trace(tr: np.ndarray, signers: int, tw: int, wallets: int) -> dict:
+    """The trace words of mpcxh_bench_signing / mpcxh_ecdsa_sign_batch for tw
+    traced wallets of `wallets`, decoded (see bench_signing)."""
+    npairs = signers * (signers - 1)
     pairs = []
     for p in range(npairs):
         rows = []
@@ -375,7 +394,7 @@ def bench_signing(nodes: Sequence[Dict[str, int]], signers: int, wallets: int, s
         r, s = words_to_ints(tr[o:o + 16].reshape(2, 8))
         sigs.append((r, s, int(tr[o + 16])) if r else None)
         gg.append(words_to_ints(tr[o + 17:o + 25].reshape(1, 8))[0] if r else None)
-    return stats, {"wallets": [t * wallets // tw for t in range(tw)], "pairs": pairs, "sigs": sigs, "gg18": gg}
+    return {"wallets": [t * wallets // tw for t in range(tw)], "pairs": pairs, "sigs": sigs, "gg18": gg}
 
 
 def bench_signing_mta(nodes, signers: int, wallets: int, seed: int = 0x5167) -> dict:

@@ -13,10 +13,10 @@ import numpy as np
 
 from . import host as _host
 from .mpcx import ints_to_words, words_to_ints
+from .wire import DLN_ITERATIONS, FAC_FIELDS, MOD_ITERATIONS  # the proofs' shapes, as they travel
+from .wire import PAILLIER_PROOF_PARTS as PAILLIER_ITERATIONS
 
 W = 160  # integer width in 32-bit words (FacProof's v reaches ~4.9 kbit)
-DLN_ITERATIONS, MOD_ITERATIONS = 128, 80
-FAC_FIELDS = ["P", "Q", "A", "B", "T", "Sigma", "Z1", "Z2", "W1", "W2", "V"]
 
 _vp, _u32, _u64, _i = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_int
 
@@ -27,6 +27,11 @@ SIGNATURES = [
     ("mpcxh_mod_verify_batch", _i, [_u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("mpcxh_fac_prove_batch", _i, [_u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
     ("mpcxh_fac_verify_batch", _i, [_u32, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _vp, _vp]),
+    ("mpcxh_paillier_prove_batch", _i, [_u32, _vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp]),
+    ("mpcxh_paillier_proof_verify_batch", _i, [_u32, _vp, _u32, _vp, _vp, _vp, _vp]),
+    # bound here beside the other mpcxh_party_t entry points; mpcium_amd/ecdsa.py is its caller
+    ("mpcxh_ecdsa_keygen_batch", _i, [_u32, _vp, _u32, _u32, _vp, _u32, _u32, _vp, _u32, _vp, _vp, ctypes.c_int64, _i,
+                                      _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("mpcxh_bench_keygen_proofs", _i, [_u32, _vp, _u32, _u32, _u64, _u32, _vp, _vp]),
     ("mpcxh_bench_keygen_reshare", _i, [_u32, _vp, _u32, _u32, _u64, _u32, _i, ctypes.c_int64, _vp, _vp]),
 ]
@@ -156,9 +161,72 @@ def fac_verify(sessions: Sequence[bytes], N0: int, NCap: int, s: int, t: int, pf
     return [bool(x) and not w for x, w in zip(ok, wide)]
 
 
+def _statements(ks: Sequence[int], pubs: Sequence[tuple]):
+    if len(ks) != len(pubs):
+        raise ValueError("one k and one public key per proof")
+    if any(not (0 <= c < (1 << 256)) for p in pubs for c in p):
+        raise ValueError("a public-key coordinate outside [0, 2^256)")
+    K = _col(ks) if ks else np.zeros((1, W), dtype="<u4")
+    P = np.ascontiguousarray(ints_to_words([p[0] | (p[1] << 256) for p in pubs], 16)) if pubs else \
+        np.zeros((1, 16), dtype="<u4")
+    return K, P
+
+
+def paillier_prove(N: int, P: int, Q: int, ks: Sequence[int], pubs: Sequence[tuple],
+                   retries: bool = False):
+    """(*PrivateKey).Proof(k, pub) under the key N = P Q for every (ks[i],
+    pubs[i]) -> [[y_0..y_12]]; retries=True: also each proof's final GenerateXs
+    retry counter."""
+    n = len(ks)
+    K, pb = _statements(ks, pubs)
+    args = [_one(v) for v in (N, P, Q)]
+    y = np.zeros((max(n, 1), PAILLIER_ITERATIONS * W), dtype="<u4")
+    rt = np.zeros(max(n, 1), dtype="<u4")
+    _host._check(lib().mpcxh_paillier_prove_batch(W, *[a.ctypes.data for a in args], n, K.ctypes.data,
+                                                  pb.ctypes.data, y.ctypes.data, rt.ctypes.data))
+    out = _rows(y[:n], n, PAILLIER_ITERATIONS) if n else []
+    return (out, [int(v) for v in rt[:n]]) if retries else out
+
+
+def paillier_verify(N: int, ks: Sequence[int], pubs: Sequence[tuple], pfs: Sequence[Sequence[int]]) -> List[bool]:
+    """(*Proof).Verify(N, k, pub) per proof. A proof that is not 13 values, or
+    holds one wider than the batch's W words, is rejected here."""
+    n = len(pfs)
+    if len(ks) != n:
+        raise ValueError("one k and one public key per proof")
+    K, pb = _statements(ks, pubs)
+    lim = 1 << (32 * W)
+    bad = [len(p) != PAILLIER_ITERATIONS or any(not (0 <= v < lim) for v in p) for p in pfs]
+    y = _col([v for p, b in zip(pfs, bad) for v in ([0] * PAILLIER_ITERATIONS if b else p)]) if n else \
+        np.zeros((1, W), dtype="<u4")
+    ok = np.zeros(max(n, 1), dtype=np.uint8)
+    Nw = _one(N)
+    _host._check(lib().mpcxh_paillier_proof_verify_batch(W, Nw.ctypes.data, n, K.ctypes.data, pb.ctypes.data,
+                                                         y.ctypes.data, ok.ctypes.data))
+    return [bool(x) and not b for x, b in zip(ok[:n], bad)]
+
+
 class _Party(ctypes.Structure):
     _fields_ = [("N", _vp), ("LambdaN", _vp), ("P", _vp), ("Q", _vp), ("NTilde", _vp), ("h1", _vp), ("h2", _vp),
                 ("alpha", _vp), ("beta", _vp), ("p", _vp), ("q", _vp)]
+
+
+def party_array(parties: Sequence[dict]):
+    """(mpcxh_party_t array of W-word integers, the buffers it points into) for
+    nodes given as dicts with N, LambdaN, P, Q, NTildei, H1i, H2i, Alpha, Beta,
+    p, q. Keep the second value alive for the duration of the call."""
+    keep = []
+
+    def ptr(v):
+        a = _one(v)
+        keep.append(a)
+        return a.ctypes.data
+
+    arr = (_Party * len(parties))()
+    for k, n in enumerate(parties):
+        arr[k] = _Party(ptr(n["N"]), ptr(n["LambdaN"]), ptr(n["P"]), ptr(n["Q"]), ptr(n["NTildei"]), ptr(n["H1i"]),
+                        ptr(n["H2i"]), ptr(n["Alpha"]), ptr(n["Beta"]), ptr(n["p"]), ptr(n["q"]))
+    return arr, keep
 
 
 KEYGEN_STATS = ["prove_s", "verify_s", "total_s", "sessions", "parties", "proofs", "verifications", "failures",
@@ -180,17 +248,7 @@ def bench_keygen_proofs(parties: Sequence[dict], sessions: int, seed: int = 0x6B
     "digests": {(i, "dln1"|"dln2"|"mod"): d, (i, "fac", j): d}, "verified":
     count} + for reshare waves "vss": {"old": [d_i], "new_shares": d,
     "passed": count}]."""
-    keep = []
-
-    def ptr(v):
-        a = _one(v)
-        keep.append(a)
-        return a.ctypes.data
-
-    arr = (_Party * len(parties))()
-    for k, n in enumerate(parties):
-        arr[k] = _Party(ptr(n["N"]), ptr(n["LambdaN"]), ptr(n["P"]), ptr(n["Q"]), ptr(n["NTildei"]), ptr(n["H1i"]),
-                        ptr(n["H2i"]), ptr(n["Alpha"]), ptr(n["Beta"]), ptr(n["p"]), ptr(n["q"]))
+    arr, keep = party_array(parties)
     names = RESHARE_STATS if reshare else KEYGEN_STATS
     st = np.zeros(len(names), dtype=np.float64)
     n = len(parties)

@@ -22,7 +22,10 @@ Three layers, outermost first:
    ``RangeProofAlice.Bytes()``, 6 parts), ``SignRound2Message`` (c1, c2 and
    ``ProofBob.Bytes()`` 10 parts, ``ProofBobWC.Bytes()`` 12 parts),
    ``KGRound1Message`` (Paillier N, N~, h1, h2, two DLN proofs of 2x128
-   parts). Every part is a big-endian ``big.Int.Bytes()``; tss-lib's
+   parts), and the rest of keygen: ``KGRound2Message1`` (a VSS share and
+   ``ProofFac.Bytes()``, 11 parts), ``KGRound2Message2`` (the decommitment
+   and ``ProofMod.Bytes()``, 163 parts), ``KGRound3Message`` (the Paillier
+   key proof, 13 parts). Every part is a big-endian ``big.Int.Bytes()``; tss-lib's
    ``*FromBytes`` constructors reject empty parts (``common.NonEmptyMultiBytes``)
    and so does this decoder.
 
@@ -374,7 +377,84 @@ class KGRound1Message:
                    cls._dln_from(_rep_bytes(fs, 6)), cls._dln_from(_rep_bytes(fs, 7)))
 
 
-CONTENT_TYPES = {c.TYPE: c for c in (SignRound1Message1, SignRound2Message, KGRound1Message)}
+FAC_PROOF_PARTS = 11          # P, Q, A, B, T, Sigma, Z1, Z2, W1, W2, V
+MOD_ITERATIONS = 80           # modproof.Iterations: W, X[80], A, B, Z[80]
+MOD_PROOF_PARTS = 3 + 2 * MOD_ITERATIONS
+PAILLIER_PROOF_PARTS = 13     # paillier.ProofIters
+FAC_FIELDS = ["P", "Q", "A", "B", "T", "Sigma", "Z1", "Z2", "W1", "W2", "V"]
+
+
+def _rep(num: int, vals: Sequence[int]) -> bytes:
+    return b"".join(_pb_bytes(num, int_bytes(v), keep_empty=True) for v in vals)
+
+
+@dataclass
+class KGRound2Message1:
+    """ecdsa-keygen.proto: share=1, facProof=2 (repeated; facproof.ProofFac.Bytes:
+    11 parts in the order of FAC_FIELDS, each big.Int.Bytes(), so V travels as
+    its absolute value). Point to point: the receiver's VSS share and the
+    no-small-factor proof over the receiver's (N~, h1, h2). Field numbers as
+    recalled (upstream, verify)."""
+    share: int
+    fac_proof: Dict[str, int]
+    TYPE = KEYGEN_PKG + "KGRound2Message1"
+
+    def to_content(self) -> bytes:
+        if sorted(self.fac_proof) != sorted(FAC_FIELDS):
+            raise WireError("FacProof needs the 11 fields of FAC_FIELDS")
+        return _pb_bytes(1, int_bytes(self.share)) + _rep(2, [abs(self.fac_proof[f]) for f in FAC_FIELDS])
+
+    @classmethod
+    def from_content(cls, buf: bytes) -> "KGRound2Message1":
+        fs = pb_fields(buf)
+        vals = _non_empty_parts(_rep_bytes(fs, 2), FAC_PROOF_PARTS, "FacProof")
+        return cls(bytes_int(_one_bytes(fs, 1)), dict(zip(FAC_FIELDS, vals)))
+
+
+@dataclass
+class KGRound2Message2:
+    """ecdsa-keygen.proto: de_commitment=1 (repeated: the blinding value, then
+    V_0.x, V_0.y, ..), modProof=2 (repeated; modproof.ProofMod.Bytes: W, X[80],
+    A, B, Z[80]). Broadcast. Field numbers as recalled (upstream, verify)."""
+    de_commitment: List[int]
+    mod_proof: Dict[str, object]
+    TYPE = KEYGEN_PKG + "KGRound2Message2"
+
+    def to_content(self) -> bytes:
+        p = self.mod_proof
+        if len(p["X"]) != MOD_ITERATIONS or len(p["Z"]) != MOD_ITERATIONS:
+            raise WireError("ModProof needs 80 X and 80 Z values")
+        return _rep(1, self.de_commitment) + _rep(2, [p["W"], *p["X"], p["A"], p["B"], *p["Z"]])
+
+    @classmethod
+    def from_content(cls, buf: bytes) -> "KGRound2Message2":
+        fs = pb_fields(buf)
+        dc = _rep_bytes(fs, 1)
+        v = _non_empty_parts(_rep_bytes(fs, 2), MOD_PROOF_PARTS, "ModProof")
+        n = MOD_ITERATIONS
+        return cls(_non_empty_parts(dc, len(dc), "DeCommitment"),
+                   {"W": v[0], "X": v[1:1 + n], "A": v[1 + n], "B": v[2 + n], "Z": v[3 + n:]})
+
+
+@dataclass
+class KGRound3Message:
+    """ecdsa-keygen.proto: paillier_proof=1 (repeated: y_0..y_12 of
+    paillier.Proof). Broadcast. Field number as recalled (upstream, verify)."""
+    paillier_proof: List[int]
+    TYPE = KEYGEN_PKG + "KGRound3Message"
+
+    def to_content(self) -> bytes:
+        if len(self.paillier_proof) != PAILLIER_PROOF_PARTS:
+            raise WireError("Paillier proof needs 13 values")
+        return _rep(1, self.paillier_proof)
+
+    @classmethod
+    def from_content(cls, buf: bytes) -> "KGRound3Message":
+        return cls(_non_empty_parts(_rep_bytes(pb_fields(buf), 1), PAILLIER_PROOF_PARTS, "PaillierProof"))
+
+
+CONTENT_TYPES = {c.TYPE: c for c in (SignRound1Message1, SignRound2Message, KGRound1Message, KGRound2Message1,
+                                     KGRound2Message2, KGRound3Message)}
 
 
 def wire_bytes(content, from_: PartyID, to: Sequence[PartyID] = (), is_broadcast: bool = False) -> bytes:

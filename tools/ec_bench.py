@@ -30,6 +30,15 @@ adds the wall time of one eddsa.keygen_batch over N sessions at 2 of 3 with
 its share spent inside the GPU batches.
 
     python tools/ec_bench.py --admit --sizes 2560,25600 --keygen-sessions 10000
+
+--ecdsa-keygen-sessions N times one ecdsa.keygen_batch over N sessions at (3, 1)
+on the fixture nodes, with the parties' batches side by side and again with
+serial_launches; --ecdsa-sign-wallets N one ecdsa.sign_batch over N stored
+wallets with 2 signers and, in the same process, mta.bench_signing at N wallets.
+Each once after a warm-up, with wall time and per-kernel time. The two flags run on
+their own, without the others.
+
+    python tools/ec_bench.py --ecdsa-keygen-sessions 1000 --ecdsa-sign-wallets 1000
 """
 import argparse
 import json
@@ -55,14 +64,27 @@ def main():
                     help="time k_ed_admit (clear = 1) and the one-point k_ed_msm route with the scalar 8 c")
     ap.add_argument("--keygen-sessions", type=int, default=0,
                     help="time eddsa.keygen_batch over this many sessions at 2 of 3")
+    ap.add_argument("--ecdsa-keygen-sessions", type=int, default=0,
+                    help="time ecdsa.keygen_batch over this many sessions at (3, 1) on the fixture nodes")
+    ap.add_argument("--ecdsa-sign-wallets", type=int, default=0,
+                    help="time ecdsa.sign_batch over this many stored wallets with 2 signers, and "
+                         "mta.bench_signing at the same count beside it")
     args = ap.parse_args()
+    if (args.ecdsa_keygen_sessions or args.ecdsa_sign_wallets) and (
+            args.points or args.admit or args.keygen_sessions or args.sign_wallets or args.curve != "secp256k1"):
+        ap.error("--ecdsa-keygen-sessions / --ecdsa-sign-wallets run on their own: "
+                 "not with --points, --curve, --admit, --keygen-sessions or --sign-wallets")
     from mpcium_amd import mpcx
     from oracle import tss_ref as T
     mpcx.init(0)
     rng = random.Random(7)
     n = T.SECP_N
-    pts = [T.scalar_base_mult(rng.randrange(1, n)) for _ in range(64)]
     out = {"lib": os.environ.get("MPCX_LIB_PATH", "mpcium_amd/libmpcx.so"), "rows": []}
+    if args.ecdsa_keygen_sessions or args.ecdsa_sign_wallets:
+        ecdsa_rows(args, mpcx, rng, out)
+        print(json.dumps(out))
+        return
+    pts = [T.scalar_base_mult(rng.randrange(1, n)) for _ in range(64)]
 
     def timed(kind, fn, items):
         mpcx.set_option("kernel_stats", 1)
@@ -252,6 +274,74 @@ def admit_rows(args, mpcx, rng, out):
         row = {"keygen_sessions": S, "threshold": 1, "parties": 3, "wall_s": round(wall, 4),
                "gpu_batches_s": round(r["gpu_s"], 4), "gpu_share": round(r["gpu_s"] / wall, 3),
                "kernel_ms_launches": kern, "keygens_per_s": round(S / wall)}
+        out["rows"].append(row)
+        print(json.dumps(row), flush=True)
+
+
+def ecdsa_rows(args, mpcx, rng, out):
+    """--ecdsa-keygen-sessions N: wall time, time inside the GPU batch calls and
+    per-kernel time of one ecdsa.keygen_batch at (3, 1) on the three fixture
+    nodes, once after a warm-up. --ecdsa-sign-wallets N: the same of one
+    ecdsa.sign_batch over N stored wallets (from a keygen of N sessions when both
+    are given, else of 8) with 2 signers, and of mta.bench_signing at N wallets
+    in the same process: the two paths differ in the W_i batch and the Lagrange
+    arithmetic only."""
+    import time
+
+    from mpcium_amd import ecdsa, host, mta
+    host.init(0)
+    with open(os.path.join(ROOT, "tests", "golden", "node_preparams.json")) as f:
+        nodes = [{k: int(v, 16) for k, v in nd.items() if isinstance(v, str) and k != "paillier_source"}
+                 for nd in json.load(f)["nodes"]]
+    ids = [1, 2, 3]
+
+    def measured(fn):
+        mpcx.set_option("kernel_stats", 1)
+        mpcx.kernel_stats(reset=True)
+        t0 = time.perf_counter()
+        r = fn()
+        wall = time.perf_counter() - t0
+        ks = mpcx.kernel_stats()
+        mpcx.set_option("kernel_stats", 0)
+        kern = {f'{k["kind"]}/{k.get("geom", 0)}': (round(k["kernel_ms"], 3), k["launches"]) for k in ks["kernels"]}
+        return r, wall, kern
+
+    def sessions(count, base):
+        return [{"session": rng.randbytes(32), "readers": [base + 3 * s + i for i in range(3)]} for s in range(count)]
+
+    wallets = None
+    if args.ecdsa_keygen_sessions:
+        S = args.ecdsa_keygen_sessions
+        ecdsa.keygen_batch(nodes, sessions(min(S, 16), 1 << 20), 1, ids)  # warm-up
+        ss = sessions(S, 1 << 24)
+        for serial in (False, True):  # the parties' batches side by side, then every launch after the one before
+            r, wall, kern = measured(lambda: ecdsa.keygen_batch(nodes, ss, 1, ids, serial_launches=serial))
+            assert r["status"] == [0] * S
+            wallets = r["wallets"]
+            row = {"ecdsa_keygen_sessions": S, "parties": 3, "threshold": 1, "serial_launches": serial,
+                   "wall_s": round(wall, 3), "gpu_s": round(r["gpu_s"], 3), "sessions_per_s": round(S / wall, 1),
+                   "kernel_ms_launches": kern}
+            out["rows"].append(row)
+            print(json.dumps(row), flush=True)
+    if args.ecdsa_sign_wallets:
+        W = args.ecdsa_sign_wallets
+        if wallets is None:
+            wallets = ecdsa.keygen_batch(nodes, sessions(8, 1 << 22), 1, ids)["wallets"]
+        ws = [ecdsa.wallet_for_signing(wallets[i % len(wallets)], [0, 1], rng.randrange(1, ecdsa.SECP_N),
+                                       rng.randbytes(32)) for i in range(W)]
+        ecdsa.sign_batch(nodes[:2], ws[:min(W, 64)], 0x51)  # warm-up
+        r, wall, kern = measured(lambda: ecdsa.sign_batch(nodes[:2], ws, 0x52))
+        assert r["status"] == [0] * W
+        row = {"ecdsa_sign_wallets": W, "signers": 2, "wall_s": round(wall, 3), "driver_total_s": round(r["stats"]["total_s"], 3),
+               "engine_busy_s": round(r["stats"]["engine_busy_s"], 3), "signatures_per_s": round(W / wall, 1),
+               "kernel_ms_launches": kern}
+        out["rows"].append(row)
+        print(json.dumps(row), flush=True)
+        st, wall, kern = measured(lambda: mta.bench_signing(nodes, 2, W, seed=0x53))
+        assert st["signatures"] == W and st["verified"] == W
+        row = {"bench_signing_wallets": W, "signers": 2, "wall_s": round(wall, 3), "driver_total_s": round(st["total_s"], 3),
+               "engine_busy_s": round(st["engine_busy_s"], 3), "signatures_per_s": round(W / wall, 1),
+               "kernel_ms_launches": kern}
         out["rows"].append(row)
         print(json.dumps(row), flush=True)
 
