@@ -150,21 +150,33 @@ def test_each_geometry_forced(gpu, paillier_key, geom):
     """Every geometry of the 2048-bit (1, 3, 5) and 4096-bit (2, 4, 6) classes:
     quad-per-operand, lane-pair (5: the 2048-bit main geometry), narrow and
     mid layouts, each forced for shared and per-operand exponents and the
-    fused multiplier."""
+    fused multiplier. choose_geom falls back to the class's full-width geometry
+    when the forced one does not serve a launch, so kernel_stats must show that
+    each call ran as one launch in the forced geometry."""
     N = paillier_key["N"]
     m = N * N if geom in (2, 4, 6) else N
     rng = random.Random(geom)
+
+    def ran_forced(call):
+        gpu.kernel_stats(reset=True)
+        out = call()
+        ks = [k for k in gpu.kernel_stats(reset=True)["kernels"] if k["kind"].startswith("modexp") and k["launches"]]
+        assert len(ks) == 1 and ks[0]["launches"] == 1 and ks[0]["geom"] == geom, ks
+        return out
+
     gpu.set_option("force_geom", geom)
+    gpu.set_option("kernel_stats", 1)
     try:
         mod = gpu.Modulus(m)
         xs = [rng.randrange(m) for _ in range(40)]
         es = [rng.getrandbits(rng.choice([1, 17, 256, 2048])) for _ in xs]
-        assert mod.exp(xs, N) == [pow(x, N, m) for x in xs]
-        assert mod.exp(xs, es) == [pow(x, e, m) for x, e in zip(xs, es)]
+        assert ran_forced(lambda: mod.exp(xs, N)) == [pow(x, N, m) for x in xs]
+        assert ran_forced(lambda: mod.exp(xs, es)) == [pow(x, e, m) for x, e in zip(xs, es)]
         cs = [rng.randrange(m) for _ in xs]
-        assert mod.exp_mul(xs, es, cs) == [c * pow(x, e, m) % m for x, e, c in zip(xs, es, cs)]
+        assert ran_forced(lambda: mod.exp_mul(xs, es, cs)) == [c * pow(x, e, m) % m for x, e, c in zip(xs, es, cs)]
         mod.release()
     finally:
+        gpu.set_option("kernel_stats", 0)
         gpu.set_option("force_geom", -1)
 
 
