@@ -471,7 +471,9 @@ int mpcx_sync(void* stream);
  *                Montgomery reduction on the i8 matrix cores (round 5: config 2
  *                457K vs 378K modexp/s, profiles/r05/mx/); 2 adds the 2048-bit
  *                lane-pair geometry, which measured slower (1.22M vs 1.40M
- *                2048-bit modexp/s, keygen -7%: profiles/r05/mx/g5/).
+ *                2048-bit modexp/s, keygen -7%: profiles/r05/mx/g5/), for
+ *                moduli of up to 2069 bits (R = 2^2072 >= 8m; a 2070-bit
+ *                modulus keeps k_modexp in that geometry).
  *                Multi-batch launches of the 4096-bit main geometry use it too
  *                (k_modexp_multi_mx) when every group has >= "mx_seg_min"
  *                operands (default 64 since round 6: six interleaved rounds

@@ -1366,6 +1366,14 @@ bool runs_on_mx(int g, uint32_t total, uint32_t min_seg, bool multi) {
   return g_mx && has_kernel && total >= g_mx_min && (!multi || min_seg >= g_mx_seg_min);
 }
 
+// Can montmul_mx in geometry g serve modulus mod? Its result is (T + q m) / R + m with
+// |q| <= R/2 (1 + 2^-10): at most A B / R + (3/2 + 2^-11) m, so operands below 2.01 m
+// give a result below 2.01 m only if R >= 8m. R > 4m, which the CIOS product needs
+// (geom_serves), is not enough: with R = 4m + 4 the values of a squaring chain grow
+// past R within a few products (tests/test_mx_model_cpu.py). Geometry 2 always has
+// R = 2^4144 >= 2^48 m; geometry 5 (R = 2^2072) leaves its 2070-bit moduli to k_modexp.
+bool mx_serves(int g, const mpcx_modulus_s* mod) { return mod->bits + 3u <= (uint32_t)MPCX_GEOM_RBITS(g); }
+
 // Launch-time model of the 4096-bit class's geometries, measured on MI355X
 // (tools/geom_sweep.py, profiles/r02/geom_sweep/): a launch of W wavefronts
 // takes about c0 + s * k with k = ceil(W / SIMDs) wavefronts per SIMD, in units
@@ -2051,13 +2059,14 @@ static int modexp_enqueue(int di, Lane& lane, mpcx_mod_t mod, uint32_t count, co
   // the model's mx input asks about the main geometry this batch would get, the
   // full-width one where the configured main cannot serve it (the multi path
   // asks about the class's default main geometry)
-  const bool mx_ok = runs_on_mx(main_geom_for(mod, ops_fit), count, count, false);
+  const int gmain = main_geom_for(mod, ops_fit);
+  const bool mx_ok = runs_on_mx(gmain, count, count, false) && mx_serves(gmain, mod);
   const int geom = choose_geom(dev, cls, count, geom_serves(g_main_geom[cls], mod, ops_fit), forced_serves, mx_ok);
   const uint32_t G = (uint32_t)MPCX_GEOM_G(geom), K = (uint32_t)MPCX_GEOM_K(geom);
   const uint32_t waves = (count + G - 1) / G;
   // a shared exponent's sliding-window schedule lives after the tables
   const bool use_sched = exp_shared && exp_bits > 0 && g_sched_width > 0;
-  const bool mx = runs_on_mx(geom, count, count, false);
+  const bool mx = runs_on_mx(geom, count, count, false) && mx_serves(geom, mod);
   // m = N^2 with a shared exponent and no multiplier: k_modexp_nsq (N-adic pairs,
   // the same wavefront split as geometry 2) in place of k_modexp_mx
   const uint32_t* dnsq = nullptr;
@@ -2341,6 +2350,7 @@ int mpcx_modexp_multi_batch(uint32_t n_groups, const mpcx_modexp_group_t* gs) {
   const bool mx_ok = runs_on_mx(MPCX_MAIN_GEOM(cls), (uint32_t)total, min_seg, true);
   const int geom = choose_geom(dev, cls, (uint32_t)total, main_ok, forced_ok, mx_ok);
   const uint32_t G = (uint32_t)MPCX_GEOM_G(geom), K = (uint32_t)MPCX_GEOM_K(geom);
+  // (geometry 2 only: every modulus of its class passes mx_serves)
   const bool mx = runs_on_mx(geom, (uint32_t)total, min_seg, true);
   // host-side layout of the packed inputs and outputs (words)
   struct Seg {

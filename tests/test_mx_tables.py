@@ -6,7 +6,9 @@ kernel relies on are checked on edge operands as well as random ones:
     |q| <= R/2 (1 + 2^-10), and every radix-2^7 byte of it is a valid signed i8;
   - every i8 column sum fits i32;
   - the carry out of the low half, rounded from its top four column sums, is exact;
-  - U + m (the kernel's result) lies in (0, 2m) and is A B R^-1 mod m.
+  - U + m (the kernel's result) lies in (0, 2m) and is A B R^-1 mod m;
+  - the digits emitted for it lie in (-2^16, 2^28 + 2^16) (montmul_mx_digits; the batched
+    model with mx_readback's passes is tests/test_mx_model_cpu.py).
 """
 import random
 
@@ -70,7 +72,8 @@ def conv(a, b, lo, hi):
     return out
 
 
-def montmul_mx_model(a, b, m, L=148):
+def montmul_mx_digits(a, b, m, L=148):
+    """(the L digits mx_reduce emits for U + m, R), every bound asserted on the way"""
     N7 = 4 * L
     RBITS = DB * L
     R = 1 << RBITS
@@ -105,7 +108,14 @@ def montmul_mx_model(a, b, m, L=148):
         cin = hi
     U = sum(v << (28 * i) for i, v in enumerate(u))
     assert U == (T + q * m) // R + m
-    return U, R
+    # one carry step of |carry| < 2^16 on digits below 2^28 (mx_readback's precondition)
+    assert all(-(1 << 16) < v < (1 << 28) + (1 << 16) for v in u)
+    return u, R
+
+
+def montmul_mx_model(a, b, m, L=148):
+    u, R = montmul_mx_digits(a, b, m, L)
+    return sum(v << (28 * i) for i, v in enumerate(u)), R
 
 
 @pytest.mark.parametrize("L", [148, 74])
